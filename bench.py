@@ -11,11 +11,16 @@ One "eval" = one (task, particle) LML + gradient.
     python bench.py --gpus 1 --steps 200 --warmup 10
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus 8 --steps 200 --warmup 10 [--scaling strong]
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs bench_outputs
 
 --scaling weak (default): every rank holds 1024 tasks (global batch 1024 x N); --scaling strong: 1024 tasks in total, sharded
 over the N ranks (cfg #3 as BASELINE.json words it).  Either way the score [20 x 2534] (+ 20 likelihood sums) is summed with
 ONE all-reduce per step.  --config 2 | 4 | 5 times the other BASELINE configurations the same way (parity-test cases; the
 headline metric is config 3).  Prints ONE JSON line on rank 0.
+
+--dump-outputs DIR: rank 0 writes what the last timed step computed (the learner's parameters and optimizer state after it, the
+step's likelihood / loss; cfg #5: the LML and its gradients) as DIR/<name>.npy, for comparing two builds output for output.  The
+warm-up then always runs its longest length, so that the timed steps start from the same state in every run.
 """
 import argparse
 import json
@@ -34,6 +39,8 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s m
 FP32_PEAK_TFLOPS = 157.3       # fp32 vector peak == fp32-input MFMA peak (MI355X_MICROARCH.md)
 FP64_PEAK_TFLOPS = 78.6        # fp64 matrix peak: AMD's MI355X figure; tools/mfma_peak.hip measures what v_mfma_f64_16x16x4 sustains
 STEADY_STEPS = 200            # the extra region behind the timed one (the line's `steady` object)
+WARM_CHUNKS = 40              # at most this many untimed 128-step chunks in front of the timed region
+DUMP_BYTES = 64 * 10 ** 6     # --dump-outputs: at most this much in all
 PMC_PROFILE = os.path.join('profiles', 'r06_pmc_hbm_traffic.json')
 DENSE_PMC_PROFILE = os.path.join('profiles', 'r06_dense_pmc_hbm_traffic.json')
 
@@ -51,6 +58,20 @@ def make_tasks(n_tasks, n, d, seed0=1000):
         Y = slope * xm + amp * np.sin(1.5 * (xm - x_shift)) + y_shift + 0.1 * rs.normal(size=(n, 1))
         tasks.append((X, Y))
     return tasks
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: {name: tensor} -> out_dir/<name>.npy, float64 where the tensor is fp64, else float32.  An array above its
+    share of DUMP_BYTES is replaced by a fixed sample of its elements (flattened; seeded, so the same elements in every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays)) - 4096                   # (room for the .npy header)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            idx = np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def gp_flops(n, f):
@@ -176,6 +197,7 @@ def main():
     ap.add_argument('--config', type=lambda v: int(v) if v.isdigit() else v, choices=[1, 2, 3, 4, 5, 'ref_svgd', 'ref_vi', 'shard128', 'ref_map'], default=3)
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-other-configs', action='store_true')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None)
     args = ap.parse_args()
 
     rank = int(os.environ.get('RANK', '0'))
@@ -231,11 +253,12 @@ def main():
         # boot: hipGraphLaunch measured at 0.18 ms per step against 0.03 ms a minute later, enough to starve a 0.5 ms step).  More
         # untimed steps, in chunks, until two consecutive chunks take the same time (or 5 s have passed); every rank runs the same
         # number of chunks.
-        prev, t_warm = None, time.perf_counter()
-        for _ in range(40):
+        prev, t_warm, chunks = None, time.perf_counter(), 0
+        for _ in range(WARM_CHUNKS):
             t_c = time.perf_counter()
             wl['run'](128)                                # (16 + 112 steps: engine.first_chunk; the second look needs a chunk of >= 60)
             barrier()
+            chunks += 1
             cur = time.perf_counter() - t_c
             stable = prev is not None and abs(cur - prev) <= 0.03 * prev and time.perf_counter() - t_warm >= 1.0
             flag = torch.tensor([1.0 if (stable or time.perf_counter() - t_warm > 5.0) else 0.0], device='cuda')
@@ -244,6 +267,10 @@ def main():
             if float(flag.item()) > 0:
                 break
             prev = cur
+        if args.dump_outputs and chunks < WARM_CHUNKS:
+            # how many chunks the loop ran depends on timing: the rest of them, so that the timed steps start from the same state
+            wl['run'](128 * (WARM_CHUNKS - chunks))
+            barrier()
         t0 = time.perf_counter()
         wl['run'](args.steps)
         t_issued = time.perf_counter()                   # the host has issued every step (nothing synchronises inside)
@@ -254,6 +281,10 @@ def main():
             tt = torch.tensor([elapsed], dtype=torch.float64, device='cuda')
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = float(tt.item())
+        if args.dump_outputs and primary:
+            if rank == 0:
+                dump_outputs(args.dump_outputs, wl['outputs']())
+            barrier()
         # the steady state, driver-visible: one more region of STEADY_STEPS steps right behind the --steps region (same workload, same
         # bracketing).  The top-level value stays the --steps region's; short regions also pay the clock ramp after the idle barrier
         # (tools/README.md), which this one dilutes.
@@ -695,6 +726,18 @@ def _mode(model):
     return dict({'graph': bool(sm.use_graph) if sm.use_graph is not None else True}, **(sm.timings or {}))
 
 
+def _svgd_outputs(model):
+    return lambda: {'particles': model.particles, 'exp_avg': model.exp_avg, 'exp_avg_sq': model.exp_avg_sq, 'lik': model._lik}
+
+
+def _map_outputs(model):
+    return lambda: {'theta': model.theta, 'exp_avg': model.exp_avg, 'exp_avg_sq': model.exp_avg_sq, 'loss': model._g_loss}
+
+
+def _vi_outputs(model):
+    return lambda: {'posterior': model.posterior, 'exp_avg': model.exp_avg, 'exp_avg_sq': model.exp_avg_sq, 'loss': model._loss}
+
+
 def wl_cfg3(world, scaling, M, L):
     T_global = TASKS * world if scaling == 'weak' else TASKS
     model = M.GPRegressionMetaLearnedSVGD(make_tasks(T_global, N_CTX, DIM), num_particles=PARTICLES, covar_module='NN',
@@ -703,7 +746,7 @@ def wl_cfg3(world, scaling, M, L):
     w = net_macs(DIM, (32, 32), 1) + net_macs(DIM, (32, 32), 2)                 # 2400 MAC per point over both networks
     w1 = 2 * DIM * 32                                                           # ... of which the first layers (recomputed by the backward)
     return dict(run=model._train_steps, evals_per_step=T_global * PARTICLES, dtype='f32', mode=lambda: _mode(model),
-                finite=lambda: bool(torch.isfinite(model.particles).all()),
+                finite=lambda: bool(torch.isfinite(model.particles).all()), outputs=_svgd_outputs(model),
                 flops={'gp_lml_fwdbwd': (gp_flops(N_CTX, 2) * ev,) * 2, 'mlp_fwd': (2 * N_CTX * w * ev,) * 2,
                        'mlp_bwd': (4 * N_CTX * w * ev, (4 * w + 2 * w1) * N_CTX * ev)},
                 pmc_keys={'gp_lml_fwdbwd': 'gp_reg_kernel', 'mlp_fwd': 'mlp_fused_fwd', 'mlp_bwd': 'mlp_fused_bwd'},
@@ -720,6 +763,7 @@ def wl_cfg1(world, scaling, M, L):
     w = net_macs(1, (32, 32), 1) + net_macs(1, (32, 32), 2)
     ev = 5 / world
     return dict(run=model._train_steps, evals_per_step=5, dtype='f32', finite=lambda: bool(torch.isfinite(model.theta).all()), mode=lambda: _mode(model),
+                outputs=_map_outputs(model),
                 metric='task-GP LML+grad evals/sec (PACOH-MAP demo: 20 tasks x 5 points, 5 per iteration)',
                 flops={'gp_lml_fwdbwd': (gp_flops(5, 2) * ev,) * 2, 'mlp_fwd': (2 * 5 * w * ev,) * 2, 'mlp_bwd': (4 * 5 * w * ev, 6 * 5 * w * ev),
                        'map_persist': ((gp_flops(5, 2) + 6 * 5 * w) * ev,) * 2},        # (the whole iteration is one kernel: pacoh_map_persist)
@@ -735,6 +779,7 @@ def wl_cfg2(world, scaling, M, L):
     ev = T / world
     w = net_macs(1, (32, 32), 1)
     return dict(run=model._train_steps, evals_per_step=T, dtype='f32', finite=lambda: bool(torch.isfinite(model.theta).all()), mode=lambda: _mode(model),
+                outputs=_map_outputs(model),
                 metric='task-GP LML+grad evals/sec (PACOH-MAP, 256 tasks, n_ctx=32, d=1, SE kernel)',
                 flops={'gp_lml_fwdbwd': (gp_flops(32, 1) * ev,) * 2, 'mlp_fwd': (2 * 32 * w * ev,) * 2,
                        'mlp_bwd': (4 * 32 * w * ev, 6 * 32 * w * ev),
@@ -750,6 +795,7 @@ def wl_cfg4(world, scaling, M, L):
     ev = T * S / world
     w = net_macs(1, (32, 32), 1) + net_macs(1, (32, 32), 2)
     return dict(run=model._train_steps, evals_per_step=T * S, dtype='f32', finite=lambda: bool(torch.isfinite(model.posterior).all()), mode=lambda: _mode(model),
+                outputs=_vi_outputs(model),
                 gpu_only=_vi_gpu_only(model),
                 metric='task-GP LML+grad evals/sec (PACOH-VI, 512 tasks, n_ctx=128, 10 posterior samples)',
                 flops={'gp_lml_fwdbwd': (gp_flops(128, 2) * ev,) * 2, 'mlp_fwd': (2 * 128 * w * ev,) * 2,
@@ -774,7 +820,9 @@ def wl_cfg5(world, scaling, M, L):
         for _ in range(k):
             last['out'] = L.gp_lml_fwdbwd(X, 1, None, L.MEAN_ZERO, Y, 1, ls, os1, nz, B, 1)
     fl = gp_flops(n, d) * B
+    names = ('lml', 'd_z', 'd_mean', 'd_ls', 'd_os', 'd_noise')            # (L.gp_lml_fwdbwd's results; info is a status code)
     return dict(run=run, evals_per_step=B * world, dtype='f64', finite=lambda: bool(torch.isfinite(last['out'][0]).all()),
+                outputs=lambda: {k: v for k, v in zip(names, last['out']) if v is not None},
                 metric='task-GP LML+grad evals/sec (n_ctx=512, d=8, fp64)',
                 flops={'gp_lml_dense': (fl, fl)},
                 describe='cfg#5 large-context stress: %d GPs x n_ctx=512, d=8, fp64, SE kernel, LML + gradients (Gram -> MFMA-panel '
@@ -824,7 +872,7 @@ def wl_ref_svgd(world, scaling, M, L):
                                           optimizer='Adam', lr=1e-3, lr_decay=0.98, kernel='RBF', bandwidth=0.1, num_particles=10,
                                           task_batch_size=2)
     return dict(run=model._train_steps, evals_per_step=20, dtype='f32', mode=lambda: _mode(model),
-                finite=lambda: bool(torch.isfinite(model.particles).all()),
+                finite=lambda: bool(torch.isfinite(model.particles).all()), outputs=_svgd_outputs(model),
                 metric='task-GP LML+grad evals/sec (PACOH-SVGD at the reference launcher\'s defaults: 2 tasks x 10 particles per step, n_ctx=20)',
                 flops=_ref_launcher_flops(10),
                 describe='PACOH-SVGD step at the defaults of experiments/meta_GPR_SVGD_base_exp.py: 20 sinusoid tasks x 20 points, '
@@ -855,7 +903,7 @@ def wl_ref_vi(world, scaling, M, L):
         return round(ms, 5) if bool(torch.isfinite(m2.posterior).all()) else None
     return dict(run=model._train_steps, evals_per_step=20, dtype='f32', mode=lambda: _mode(model), gpu_only=_vi_gpu_only(model),
                 device_noise=device_noise,
-                finite=lambda: bool(torch.isfinite(model.posterior).all()),
+                finite=lambda: bool(torch.isfinite(model.posterior).all()), outputs=_vi_outputs(model),
                 metric='task-GP LML+grad evals/sec (PACOH-VI at the reference launcher\'s defaults: 2 tasks x 10 samples per step, n_ctx=20)',
                 flops=_ref_launcher_flops(10),
                 describe='PACOH-VI step at the defaults of experiments/meta_GPR_vi_base_exp.py: 20 sinusoid tasks x 20 points, '
@@ -873,6 +921,7 @@ def wl_ref_map(world, scaling, M, L):
                                       optimizer='Adam')
     w = net_macs(1, layers, 1) + net_macs(1, layers, 2)
     return dict(run=model._train_steps, evals_per_step=2, dtype='f32', finite=lambda: bool(torch.isfinite(model.theta).all()), mode=lambda: _mode(model),
+                outputs=_map_outputs(model),
                 metric='task-GP LML+grad evals/sec (PACOH-MAP at the reference launcher\'s defaults: 2 tasks x 5 points per iteration, 4 x 128 networks)',
                 flops={'gp_lml_fwdbwd': (gp_flops(5, 2) * 2,) * 2, 'mlp_fwd': (2 * 5 * w * 2,) * 2, 'mlp_bwd': (4 * 5 * w * 2, 6 * 5 * w * 2),
                        'map_task_step': ((gp_flops(5, 2) + 6 * 5 * w) * 2,) * 2},      # (forward + GP + backward in one workgroup: map_wide_kernel)

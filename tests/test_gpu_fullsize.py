@@ -146,6 +146,26 @@ def test_cfg5_large_context_256_tasks_n512_d8_fp64_all_tasks_vs_oracle(M):
         assert relerr(d_noise[t], nzr.grad.reshape(-1)[0]) < 1e-7 and relerr(d_os[t], osr.grad) < 1e-7
 
 
+def test_bench_dump_outputs_repeat(tmp_path):
+    """`python bench.py --dump-outputs DIR` (child process, twice): the timed steps start from the same state in every run, so two
+    runs with the same arguments write the same arrays -- what the last timed cfg #3 step left: particles, Adam state, likelihoods"""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for run in ('a', 'b'):
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '2', '--no-other-configs',
+                            '--no-cpu-baseline', '--dump-outputs', str(tmp_path / run)], cwd=root,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+    names = sorted(os.listdir(str(tmp_path / 'a')))
+    assert names == ['exp_avg.npy', 'exp_avg_sq.npy', 'lik.npy', 'particles.npy'] and sorted(os.listdir(str(tmp_path / 'b'))) == names
+    for name in names:
+        a, b = np.load(str(tmp_path / 'a' / name)), np.load(str(tmp_path / 'b' / name))
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.array_equal(a, b), name
+    assert np.load(str(tmp_path / 'a' / 'particles.npy')).shape[0] == 20
+
+
 def test_bench_line_contract():
     """`python bench.py` (child process) prints ONE JSON line with the driver's keys, BASELINE.json's metric, a live
     roofline object and a bounded cpu_baseline; value is consistent with ms_per_step."""

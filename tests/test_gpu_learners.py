@@ -100,7 +100,7 @@ def sample_data_nonstationary(rs, size=1):
     return X, Y
 
 
-def test_map_seed_consistency_and_state_dict_roundtrip(M):
+def test_map_seed_consistency_and_state_dict_roundtrip(M, tmp_path):
     """reference tests/test_GPR.py:173-222"""
     rs = np.random.RandomState(23)
     train = [sample_data_nonstationary(rs, 5) for _ in range(3)]
@@ -120,8 +120,8 @@ def test_map_seed_consistency_and_state_dict_roundtrip(M):
         b = M.GPRegressionMetaLearned(train, learning_mode='both', num_iter_fit=5, mean_module=mean_module, random_seed=25)
         b.meta_fit(verbose=False)
         pred_2 = b.predict(*test[0][:3])
-        torch.save(a.state_dict(), '/tmp/test_torch_serialization.pkl')
-        b.load_state_dict(torch.load('/tmp/test_torch_serialization.pkl'))
+        torch.save(a.state_dict(), str(tmp_path / 'test_torch_serialization.pkl'))
+        b.load_state_dict(torch.load(str(tmp_path / 'test_torch_serialization.pkl')))
         pred_3 = b.predict(*test[0][:3])
         assert not np.array_equal(pred_1[0], pred_2[0])
         assert np.array_equal(pred_1[0], pred_3[0]) and np.array_equal(pred_1[1], pred_3[1])

@@ -310,3 +310,28 @@ def test_bench_line_shape_with_both_scaling_legs():
             assert key in l, key
     assert out['all_reduce_us'] == 31.5 and out['vs_baseline'] is None
     assert set(out['steady']) == {'steps', 'ms_per_step', 'value'} and out['steady']['steps'] == 200       # the steady-state region behind the timed one
+
+
+def test_bench_dump_outputs_dtypes_and_size_cap(tmp_path):
+    """bench.py --dump-outputs writes <name>.npy in float32 (float64 for fp64 arrays); an array above its share of the 64 MB budget
+    is replaced by the same seeded sample of its elements on every call"""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('pacoh_bench', os.path.join(root, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(3)
+    small32, small64 = torch.randn(20, 7, generator=g), torch.randn(5, dtype=torch.float64, generator=g)
+    big = torch.arange(bench.DUMP_BYTES // 8 + 1000, dtype=torch.float64)
+    half = torch.randn(4, generator=g).half()
+    arrays = {'small32': small32, 'small64': small64, 'big': big, 'half': half}
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {k: np.load(str(tmp_path / 'a' / (k + '.npy'))) for k in arrays}
+    assert got['small32'].dtype == np.float32 and np.array_equal(got['small32'], small32.numpy())
+    assert got['small64'].dtype == np.float64 and np.array_equal(got['small64'], small64.numpy())
+    assert got['half'].dtype == np.float32 and np.array_equal(got['half'], half.float().numpy())
+    assert got['big'].dtype == np.float64 and 0 < got['big'].size < big.numel()
+    assert np.all(np.diff(got['big']) > 0) and np.array_equal(got['big'], np.unique(got['big']))       # distinct elements, in order
+    assert np.array_equal(got['big'], np.load(str(tmp_path / 'b' / 'big.npy')))                        # the same sample every time
+    assert sum(os.path.getsize(str(tmp_path / 'a' / (k + '.npy'))) for k in arrays) <= bench.DUMP_BYTES
