@@ -53,7 +53,7 @@ def _deps_mtime():
 def build_library(force=False, verbose=True, variant=None, extra_flags=()):
     """Compile every .hip source for gfx950 and link the shared library.  Returns its path.
     variant / extra_flags: an experimental build next to the product library (lib/libpacoh_gp_<variant>.so, selected at run time
-    with PACOH_LIB=<path>) compiled with additional flags, e.g. -DPACOH_EXP_...=1, for same-box A/B timing of kernel variants."""
+    with PACOH_LIB=<path>) compiled with additional flags, e.g. a diagnostic stamps build: --variant lst -DPACOH_LL_STAMPS=1."""
     obj_dir = OBJ_DIR if variant is None else OBJ_DIR + '_' + variant
     lib_path = LIB_PATH if variant is None else os.path.join(LIB_DIR, 'libpacoh_gp_%s.so' % variant)
     os.makedirs(obj_dir, exist_ok=True)

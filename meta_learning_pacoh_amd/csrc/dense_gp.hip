@@ -702,8 +702,7 @@ void launch_bgemm(const GemmArgs& ga, int Bn, hipStream_t s, int mirror = 1) {
         launch_ztz<T>((const T*)ga.A, (T*)ga.C, ga.M, ga.info, Bn, s, mirror);
         return;
     }
-    const bool tile_on = g_sw.gemm_tile;
-    if (tile_on && ga.M >= 96 && ga.N >= 96 && ga.K >= 32 && (const void*)ga.C != ga.A && (const void*)ga.C != ga.B) {
+    if (ga.M >= 96 && ga.N >= 96 && ga.K >= 32 && (const void*)ga.C != ga.A && (const void*)ga.C != ga.B) {
         const int tm = (ga.M + 127) / 128, tn = (ga.N + 127) / 128;
         const int nt = ga.symC ? tm * (tm + 1) / 2 : tm * tn;
         hipLaunchKernelGGL(gemm_tile_kernel<T>, dim3((unsigned)(nt * Bn)), dim3(256), 0, s, ga, tn, nt, Bn);
@@ -1160,10 +1159,9 @@ size_t chol_blocked_scratch(int B, int n) {
 template <typename T>
 bool chol_blocked_plan(int B, int n, size_t scratch_elems) {
     const bool on = g_sw.chol_blocked;
-    const bool mfma_on = g_sw.mfma;
     const bool ll_on = g_sw.chol_ll;
     const int dtype = sizeof(T) == 4 ? PACOH_F32 : PACOH_F64;
-    if (!on || !mfma_on || !ll_on || n <= 512 || n > 1024) return false;
+    if (!on || !ll_on || n <= 512 || n > 1024) return false;
     const int n1 = blocked_n1(n), n2 = n - n1;
     return n2 >= 97 && dense_ll_fits(n1, dtype) && dense_ll_fits(n2, dtype) && trtri_ll_fits(n1, dtype) && chol_blocked_scratch<T>(B, n) <= scratch_elems;
 }
@@ -1234,8 +1232,7 @@ template <typename T>
 int launch_trtri(T* A, const int32_t* info, int B, int n, int mpad, size_t lds, int saved_inv, hipStream_t s, const T* u = nullptr,
                  T* alpha = nullptr, int* did_alpha = nullptr, T* scratch = nullptr, size_t scratch_elems = 0) {
     // the left-looking kernel (dense_trtri_ll.hip) needs the inverse diagonal blocks the MFMA Cholesky kernels leave behind
-    const bool ll_on = g_sw.trtri_ll;
-    if (ll_on && saved_inv && n >= 97) {
+    if (saved_inv && n >= 97) {
         const int rc = trtri_ll_try(A, info, B, n, sizeof(T) == 4 ? PACOH_F32 : PACOH_F64, s, u, alpha);
         if (rc != 1) { if (did_alpha && u && alpha) *did_alpha = 1; return rc; }
         const int rb = trtri_blocked<T>(A, info, B, n, scratch, scratch_elems, s);
@@ -1337,8 +1334,7 @@ int lml_dense_impl(const void* z, int z_div, const void* mean, int mean_mode, co
         GemmArgs ga = {A, A, Wm, (long)n * n, (long)n * n, (long)n * n, n, n, n, n, n, n, 1, 0, 1, 1, 1.0, 0.0, info, 1};
         // fp64 ARD-RBF: the symmetric MFMA contraction (dense_grad_mfma.hip) reads the lower 64-tiles of W only -- the 128-tiles of
         // Z^T Z below the block diagonal are then not mirrored (268 MB of 32-byte-segment stores less per 256 x 512^2 launch)
-        const bool gm_on = g_sw.grad_mfma;
-        const bool gm_plan = gm_on && dense_grad_mfma_plan(B, n, f, kind, dtype, nn * sizeof(T));
+        const bool gm_plan = dense_grad_mfma_plan(B, n, f, kind, dtype, nn * sizeof(T));
         launch_bgemm<T>(ga, B, s, gm_plan ? 0 : 1);                         // W = Z^T Z
         const long tz = (long)B * n * f;
         hipLaunchKernelGGL(dense_scale_kernel<T>, dim3((unsigned)((tz + 255) / 256)), dim3(256), 0, s, (const T*)z, z_div, (const T*)ls, zsc,
@@ -1484,10 +1480,10 @@ static void rows_copy(const void* src, void* dst, long rows, int n_src, int n_ds
 // the context size a problem of n points is factored at: n itself, or -- 97 <= n < 1024 with rows that are no multiple of 16 bytes,
 // where the left-looking kernels (n <= 512) / the two-level path (<= 1024) would otherwise hand the size to the right-looking
 // generation (1.022 vs 0.788 ms at n = 509 fp32, profiles/r05_dense_pad_ab.txt) -- the next aligned size: the padded rows are identity
-// rows of the matrices, exactly what the kernels do for tasks of unequal length.  PACOH_DENSE_PAD=0 / PACOH_CHOL_LL=0: never.
+// rows of the matrices, exactly what the kernels do for tasks of unequal length.  PACOH_CHOL_LL=0: never.
 static int dense_padded_n(int n, int dtype) {
     const int align = dtype == PACOH_F32 ? 4 : 2;
-    if (!g_sw.dense_pad || !g_sw.chol_ll || n % align == 0) return n;
+    if (!g_sw.chol_ll || n % align == 0) return n;
     if ((n >= 97 && n < 512) || (n > 512 && n < 1024)) return (n + align - 1) / align * align;
     return n;
 }

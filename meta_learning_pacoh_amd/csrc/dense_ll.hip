@@ -193,11 +193,7 @@ __device__ __forceinline__ void chol_ll_body(T* __restrict__ A, const T* __restr
         }
     };
 
-#ifdef LL_X_CHAIN
-    if (false) {
-#else
     if (is_chain) {
-#endif
         // =========================================================== CHAIN ===========================================================
         T a[DNB];
         bool bad = false;
@@ -357,11 +353,7 @@ __device__ __forceinline__ void chol_ll_body(T* __restrict__ A, const T* __restr
             printf("chain (us): total %.1f | in quanta %.1f | per column %.1f %.1f %.1f %.1f %.1f %.1f %.1f %.1f\n", (wall_clock64() - st_t0) * 0.01, st_q * 0.01,
                    st_qc[0] * 0.01, st_qc[1] * 0.01, st_qc[2] * 0.01, st_qc[3] * 0.01, st_qc[4] * 0.01, st_qc[5] * 0.01, st_qc[6] * 0.01, st_qc[7] * 0.01);
 #endif
-#ifdef LL_X_HELPER
-    } else if (false) {
-#else
     } else if (is_helper) {
-#endif
         // =========================================================== HELPERS =========================================================
         T sacc = 0;                                               // wave 4: (L[j, 0:j] u)_lane
 #ifdef PACOH_LL_STAMPS
@@ -551,11 +543,7 @@ __device__ __forceinline__ void chol_ll_body(T* __restrict__ A, const T* __restr
             printf("helper %d (us): outside slab loop %.1f | DMA issue %.1f | dot %.1f | vmcnt wait %.1f | barrier wait %.1f\n", hidx, sh_[0] * 0.01, sh_[1] * 0.01, sh_[2] * 0.01, sh_[3] * 0.01, sh_[4] * 0.01);
 #endif
 #undef HST
-#ifdef LL_X_BULK
-    } else if (false) {
-#else
     } else {
-#endif
         // =========================================================== BULK ============================================================
         Acc acc0[4], acc1[4], la;
         const bool la_owner = bw >= 2;

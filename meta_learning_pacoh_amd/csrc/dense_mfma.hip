@@ -30,13 +30,7 @@ __device__ __forceinline__ void factor_invert_diag32(T (*Ds)[DNB + 1], T* __rest
 #pragma unroll
     for (int c = 0; c < DNB; ++c) a[c] = Ds[rr][c];
     bool bad = false;
-#ifdef PACOH_FACT_DEBUG
-    const long long tf0 = wall_clock64();
-#endif
     ElimSteps<T, 0>::run(a, invd, bad, lane);
-#ifdef PACOH_FACT_DEBUG
-    const long long tf1 = wall_clock64();
-#endif
     if (bad && lane == 0) *fail = 1;
     if (lane < 32) {
 #pragma unroll
@@ -50,9 +44,6 @@ __device__ __forceinline__ void factor_invert_diag32(T (*Ds)[DNB + 1], T* __rest
 #pragma unroll
         for (int c = 0; c < DNB; ++c) Li[rr * DLP + c] = a[c];          // (zeros above the diagonal: sums of 0 x finite)
     }
-#ifdef PACOH_FACT_DEBUG
-    if (lane == 0) { g_tdbg[0] = tf1 - tf0; g_tdbg[1] = wall_clock64() - tf1; }
-#endif
     __builtin_amdgcn_wave_barrier();
 }
 
@@ -76,20 +67,9 @@ __global__ void __launch_bounds__(NT) chol_dense_mfma_kernel(T* __restrict__ A, 
     const int r = lane & 15, g = lane >> 4;
     T* Ab = A + (size_t)blockIdx.x * n * n;
     if (tid == 0) red[16] = 0;
-#ifdef PACOH_CHOL_STAMPS
-    __shared__ double stamp_wait[2];                   // (own storage: red[96..128) is the reciprocal-pivot scratch of factor_invert_diag32)
-    if (tid == 0) { stamp_wait[0] = 0; stamp_wait[1] = 0; }
-#endif
     for (int q = tid; q < n; q += NT) rv[q] = resid[(size_t)blockIdx.x * n + q];
     T logdet_part = 0;
     __syncthreads();
-#ifdef PACOH_CHOL_STAMPS      // diagnostic build: python -m meta_learning_pacoh_amd._build --variant cst -DPACOH_CHOL_STAMPS=1 (tools/dense_quick.sh)
-    long long ph_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long tp_ = wall_clock64();
-#define CSTAMP(k) do { __syncthreads(); const long long t_ = wall_clock64(); ph_[k] += t_ - tp_; tp_ = t_; } while (0)
-#else
-#define CSTAMP(k) do {} while (0)
-#endif
 
     // One 16x16 block (ib, jb) of the trailing update A22 -= L21 L21^T, two at a time per wave so that the L2/HBM round trip of one
     // block's accumulator overlaps the other's MFMAs.
@@ -151,7 +131,6 @@ __global__ void __launch_bounds__(NT) chol_dense_mfma_kernel(T* __restrict__ A, 
             if (tid < kb0) logdet_part += t_log<T>(Ds[tid][tid]);
         }
         __syncthreads();
-        CSTAMP(1);
     }
     for (int k0 = 0; k0 < n; k0 += DNB) {
         const int kb = (n - k0 < DNB) ? (n - k0) : DNB;
@@ -181,7 +160,6 @@ __global__ void __launch_bounds__(NT) chol_dense_mfma_kernel(T* __restrict__ A, 
                 Pn[(size_t)rr * DLP + c] = (rr < m && c < kb) ? Ab[(size_t)(t0 + rr) * n + k0 + c] : T(0);
             }
             __syncthreads();
-            CSTAMP(2);
             if (tid < kb) rv[k0 + tid] = u_reg;
             // 4. L21 = A21 * L11^-T on the matrix core, in place in LDS and written back to HBM
             for (int ib = wave; ib < mb; ib += NW) {
@@ -204,14 +182,12 @@ __global__ void __launch_bounds__(NT) chol_dense_mfma_kernel(T* __restrict__ A, 
                 }
             }
             __syncthreads();
-            CSTAMP(3);
             for (int rr = tid; rr < m; rr += NT) {                          // r_rest -= L21 u_k (L21 rows from the LDS panel)
                 T sacc = rv[t0 + rr];
 #pragma unroll 8
                 for (int c = 0; c < DNB; ++c) sacc = fma(-Pn[(size_t)rr * DLP + c], (c < kb) ? rv[k0 + c] : T(0), sacc);
                 rv[t0 + rr] = sacc;
             }
-            CSTAMP(4);
             // 5a. trailing update of the block columns 0 and 1 (the next panel's own 32 columns), by every wave:
             //     q < mb -> block (q, 0); q >= mb -> block (q - mb + 1, 1)
             {
@@ -233,9 +209,6 @@ __global__ void __launch_bounds__(NT) chol_dense_mfma_kernel(T* __restrict__ A, 
             load_diag(t0, (n - t0 < DNB) ? (n - t0) : DNB, tid, NT);         // next diagonal block -> Ds: one element per thread,
             __syncthreads();                                                 // one round trip (by wave 0 alone: sixteen in a row)
             // 5b. wave 0: the next diagonal block, factored and inverted in registers | the other waves: block columns >= 2
-#ifdef PACOH_CHOL_STAMPS
-            const long long tb_ = wall_clock64();
-#endif
             if (wave == 0) {
                 const int kbn = (n - t0 < DNB) ? (n - t0) : DNB;
                 factor_invert_diag32<T>(Ds, Li, red + 32, red + 96, red + 16, tid);
@@ -258,21 +231,9 @@ __global__ void __launch_bounds__(NT) chol_dense_mfma_kernel(T* __restrict__ A, 
                     update_pair(ibs, jbs, live, t0, m);
                 }
             }
-#ifdef PACOH_CHOL_STAMPS
-            if (tid == 0) ph_[6] += wall_clock64() - tb_;
-            if (tid == 64) stamp_wait[0] += (double)(wall_clock64() - tb_);
-            if (tid == 960) stamp_wait[1] += (double)(wall_clock64() - tb_);
-#endif
         }
         __syncthreads();
-        CSTAMP(5);
     }
-#ifdef PACOH_CHOL_STAMPS
-    if (tid == 0 && blockIdx.x == 0)
-        printf("chol phases (us): load diag %.1f | factor+invert %.1f | write L11, stage panel %.1f | panel solve %.1f | resid %.1f | trailing %.1f (5b: wave 0 %.1f, wave 1 %.1f, wave 15 %.1f)\n",
-               ph_[0] * 0.01, ph_[1] * 0.01, ph_[2] * 0.01, ph_[3] * 0.01, ph_[4] * 0.01, ph_[5] * 0.01, ph_[6] * 0.01, stamp_wait[0] * 0.01, stamp_wait[1] * 0.01);
-#endif
-#undef CSTAMP
 
     // (the forward solve L u = r happened panel by panel above: rv holds u)
     T quad_part = 0;
@@ -290,9 +251,6 @@ __global__ void __launch_bounds__(NT) chol_dense_mfma_kernel(T* __restrict__ A, 
     T logdet = 0;
     for (int w = 0; w < NW; ++w) logdet += red[w];
     const bool ok = red[16] == T(0);
-#ifdef PACOH_CHOL_STAMPS
-    long long tq_ = wall_clock64();
-#endif
     if (tid == 0) {
         const T LOG2PI = T(1.8378770664093453);
         const T lp = T(-0.5) * (quad + T(2) * logdet + T(n) * LOG2PI) * scale;
@@ -320,12 +278,6 @@ __global__ void __launch_bounds__(NT) chol_dense_mfma_kernel(T* __restrict__ A, 
         }
     };
     __syncthreads();
-#ifdef PACOH_CHOL_STAMPS
-    long long bs_[3] = {0, 0, 0}, bt_ = wall_clock64();
-#define BSTAMP(k) do { __syncthreads(); const long long t_ = wall_clock64(); bs_[k] += t_ - bt_; bt_ = t_; } while (0)
-#else
-#define BSTAMP(k) do {} while (0)
-#endif
     fetch_diag(nblk - 1, Db[(nblk - 1) & 1]);
     for (int kbk = nblk - 1; kbk >= 0; --kbk) {
         const int k0 = kbk * DNB;
@@ -348,9 +300,7 @@ __global__ void __launch_bounds__(NT) chol_dense_mfma_kernel(T* __restrict__ A, 
         __syncthreads();
         if (tid < kb) rv[k0 + tid] = red[32 + tid];
         __syncthreads();
-        BSTAMP(0);
         if (kbk > 0) fetch_diag(kbk - 1, Db[(kbk - 1) & 1]);      // (no dependence on this panel's alpha)
-        BSTAMP(1);
         for (int i = tid; i < k0; i += NT) {
             T sacc = rv[i];
             if (kb == DNB) {
@@ -361,15 +311,8 @@ __global__ void __launch_bounds__(NT) chol_dense_mfma_kernel(T* __restrict__ A, 
             }
             rv[i] = sacc;
         }
-        BSTAMP(2);
     }
-#undef BSTAMP
     __syncthreads();
-#ifdef PACOH_CHOL_STAMPS
-    if (tid == 0 && blockIdx.x == 0)
-        printf("chol backward solve (us): %.1f (dot %.1f | fetch next diagonal block %.1f | update rows above %.1f)\n",
-               (wall_clock64() - tq_) * 0.01, bs_[0] * 0.01, bs_[1] * 0.01, bs_[2] * 0.01);
-#endif
     for (int q = tid; q < n; q += NT) alpha_out[(size_t)blockIdx.x * n + q] = ok ? rv[q] : T(NAN);
 }
 

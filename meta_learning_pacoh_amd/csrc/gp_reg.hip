@@ -3,7 +3,6 @@
 // launch: LDS scratch, register budget per shape, dispatch on the block count.
 // Reference lines replaced: random_gp.py:54-89, GPR_meta_mll.py:104-117 (ExactMarginalLogLikelihood + autograd through gpytorch).
 #include "gp_reg_body.h"
-#include <stdlib.h>
 
 namespace pacoh {
 
@@ -13,12 +12,7 @@ namespace pacoh {
 // wave per SIMD, and the compiler, knowing that, spread over 396 registers.  With the blocks consumed where they are produced
 // (gp_reg_body.h) the n = 128, f <= 2 kernel takes 244 registers and 4.8 KB: 0.982 -> 0.682 ms per 20 480 problems
 // (profiles/r05_gp_two_waves.txt).  f <= 4 at n = 128 would spill 200 registers at that budget and stays at one wave.
-#ifdef PACOH_GPR_W5      // A/B: five waves per SIMD for the n = 64, f <= 2 backward kernel (96 registers: 30 of them spilled)
-#define GPR_W64 5
-#else
-#define GPR_W64 4
-#endif
-#define GPR_MINW(NB, FP, BWD) ((NB) > 4 ? ((FP) == 2 || (NB) == 6 ? 2 : 1) : ((NB) == 4 && (FP) == 4 ? ((BWD) ? 2 : 3) : ((NB) == 4 && (BWD) ? GPR_W64 : 4)))
+#define GPR_MINW(NB, FP, BWD) ((NB) > 4 ? ((FP) == 2 || (NB) == 6 ? 2 : 1) : ((NB) == 4 && (FP) == 4 ? ((BWD) ? 2 : 3) : 4))
 template <int NB, int FP, bool BWD, bool HAS_OS = true>
 __global__ void __launch_bounds__(64, GPR_MINW(NB, FP, BWD)) gp_reg_kernel(GpMfmaArgs a) {
     constexpr int NP = 16 * NB;
@@ -62,9 +56,9 @@ static int launch_reg_predict(const GpMfmaArgs& a, const GpPredArgs& pa, int FP,
     return launch_status();
 }
 
-// returns 1 if this path does not apply (n > 128, f > 4, or PACOH_GP_REG=0 / PACOH_GP_REG_PREDICT=0)
+// returns 1 if this path does not apply (n > 128, f > 4)
 int gp_reg_predict_try(const GpMfmaArgs& a, const GpPredArgs& pa, hipStream_t s) {
-    if (!g_sw.gp_reg || !g_sw.gp_reg_predict || a.n > 128 || a.f > 4 || a.n < 1 || pa.m < 1) return 1;
+    if (a.n > 128 || a.f > 4 || a.n < 1 || pa.m < 1) return 1;
     const int NB = (a.n + 15) / 16;
     const int FP = a.f <= 2 ? 2 : 4;
     switch (NB) {
@@ -79,26 +73,23 @@ int gp_reg_predict_try(const GpMfmaArgs& a, const GpPredArgs& pa, hipStream_t s)
 
 template <int NB, bool BWD>
 static int launch_reg(const GpMfmaArgs& a, int FP, hipStream_t s) {
-    const unsigned pad = g_sw.lds_pad_gp > 0 ? (unsigned)g_sw.lds_pad_gp : 0u;
     if (FP == 2) {
         if constexpr (BWD && (NB == 4 || NB == 8)) {
             if (!a.os && !a.d_os) {
-                hipLaunchKernelGGL((gp_reg_kernel<NB, 2, true, false>), dim3((unsigned)a.B), dim3(64), pad, s, a);
+                hipLaunchKernelGGL((gp_reg_kernel<NB, 2, true, false>), dim3((unsigned)a.B), dim3(64), 0, s, a);
                 return launch_status();
             }
         }
-        hipLaunchKernelGGL((gp_reg_kernel<NB, 2, BWD>), dim3((unsigned)a.B), dim3(64), pad, s, a);
-    } else hipLaunchKernelGGL((gp_reg_kernel<NB, 4, BWD>), dim3((unsigned)a.B), dim3(64), pad, s, a);
+        hipLaunchKernelGGL((gp_reg_kernel<NB, 2, BWD>), dim3((unsigned)a.B), dim3(64), 0, s, a);
+    } else hipLaunchKernelGGL((gp_reg_kernel<NB, 4, BWD>), dim3((unsigned)a.B), dim3(64), 0, s, a);
     return launch_status();
 }
 
-// returns 1 if this path does not apply (n > 128, f > 4, or PACOH_GP_REG=0)
+// returns 1 if this path does not apply (n > 128, f > 4)
 int gp_reg_try(const GpMfmaArgs& a, bool bwd, hipStream_t s) {
-    if (!g_sw.gp_reg) return 1;
     // (n > 64: one wave still holds the whole matrix -- 244 registers at n = 128, two waves per SIMD -- and beats the LDS-resident
     //  kernel, which runs one wave per SIMD there and moves every block through LDS)
-    const int max_n = g_sw.gp_reg_max_n;
-    if (a.n > max_n || a.n > 128 || a.f > 4 || a.n < 1) return 1;
+    if (a.n > 128 || a.f > 4 || a.n < 1) return 1;
     const int NB = (a.n + 15) / 16;
     const int FP = a.f <= 2 ? 2 : 4;
 #define PACOH_GPR_NB(nb) case nb: return bwd ? launch_reg<nb, true>(a, FP, s) : launch_reg<nb, false>(a, FP, s);

@@ -127,22 +127,20 @@ __device__ __forceinline__ float wave_sum_(float v) {
 // SIMD): `rows` = rows of this block inside the problem (wave-uniform).  A step
 // whose four columns are all padding is not run: the padding rows are rows of the identity, exactly (their off-diagonal kernel
 // entries are exp2(-1e20) = 0), so the step would produce x = 0, Z rows = identity rows and a pivot of 1 -- which is what is set.
-// Round 6 (groups 1 and 2 of profiles/r05_gp_reg_isa_histogram.txt), -DPACOH_F16_BRANCHFREE=1: the two stores of a step
-// are `if (g == k)` regions (s_and_saveexec / s_cbranch_execz / s_or per region, 32 regions per block); in the branch-free form EVERY
+// Round 6 (groups 1 and 2 of profiles/r05_gp_reg_isa_histogram.txt) measured a branch-free form, since removed: the two
+// stores of a step are `if (g == k)` regions (s_and_saveexec / s_cbranch_execz / s_or per region, 32 regions per block); in the branch-free form EVERY
 // lane row stores its registers to a slot of its own (fs + 64 g, fs + 256 + 64 g) and the readers address lane row k's slot -- no
 // exec-mask code around a store -- and the Z entry a lane needs for the rank-4 update is read as ONE float (fs[.. + 4 r + g]) instead
 // of a 16-byte read and three selects.  Same bits; measured on the cfg #3 step, same box, two runs each
 // (profiles/r06_gp_factor16_ab.txt): 0.1449 / 0.1461 ms against 0.1452 / 0.1466 -- nothing, like round 5's permlane swap: the kernel
 // does not respond to a 3 % instruction diet.  It does respond to occupancy: the same build with the slots in a scratch array of
-// their own (10.75 KB of LDS per problem: 14 problems per CU instead of 16) ran 0.157 ms, +11 %.  Not the default.
+// their own (10.75 KB of LDS per problem: 14 problems per CU instead of 16) ran 0.157 ms, +11 %.
 // GPR_FSC: floats of per-wave LDS factor16() uses; GPR_SCR: the scratch it shares with the 16x16 transpose (tsc, 320 floats: one
 // wave, in-order LDS, and no transpose is in flight across a factor16() call).
-#ifdef PACOH_F16_BRANCHFREE
-constexpr int GPR_FSC = 512;
-#else
 constexpr int GPR_FSC = 128;
-#endif
-constexpr int GPR_SCR = GPR_FSC > 320 ? GPR_FSC : 320;
+constexpr int GPR_SCR = 320;
+static_assert(GPR_SCR >= GPR_FSC && GPR_SCR > 68 * 3 + 12 + 32 + 15 + 17 * 3,      // (the transpose's last index: twr(g = 3, r = 15) + 17 * 3)
+              "fsc (factor16) and tsc (the 16x16 transpose) alias one GPR_SCR-float array: it must hold either");
 template <bool SKIP = false>
 __device__ __forceinline__ void factor16(f32x4 Cn, f32x4& Z, float& dprod, const f32x4& nId, int r, int g, float* fs, int rows = 16) {
     f32x4 Tn = nId;                                         // -E + L Z, built up by one rank-4 MFMA per step (see below)
@@ -157,13 +155,8 @@ __device__ __forceinline__ void factor16(f32x4 Cn, f32x4& Z, float& dprod, const
         // pivot block P[c][j] = C[4k+c][4k+j] = register c of lane (r = 4k+j, g = k): wave-uniform
         const float c0 = Cn[0], c1 = Cn[1], c2 = Cn[2], c3 = Cn[3];
         const int src = (16 * k + r) * 4;
-#ifndef PACOH_F16_BRANCHFREE
         if (g == k) *reinterpret_cast<f32x4*>(fs + 4 * r) = Cn;
         const float* fk = fs;
-#else
-        *reinterpret_cast<f32x4*>(fs + 64 * g + 4 * r) = Cn;
-        const float* fk = fs + 64 * k;
-#endif
         asm volatile("" ::: "memory"); __builtin_amdgcn_wave_barrier();
         const f32x4 rtv = *reinterpret_cast<const f32x4*>(fk + 4 * r);
         const float rt0 = -rtv[0], rt1 = -rtv[1], rt2 = -rtv[2], rt3 = -rtv[3];
@@ -205,19 +198,12 @@ __device__ __forceinline__ void factor16(f32x4 Cn, f32x4& Z, float& dprod, const
             // Tn += L[:, 4k..4k+3] Z[4k..4k+3, :]: ONE MFMA (k index = the four new columns) -- A[i][kk] = L[i][4k+kk] is xg of lane
             // (i, kk); B[kk][j] = Z[4k+kk][j] lives in register kk of lane (j, k) and reaches lane (j, kk) by four lane reads.  (Forming
             // the block row of L Z as a full product with L^T kept in registers took four MFMAs per step for a 4-row result.)
-#ifndef PACOH_F16_BRANCHFREE
             if (g == k) *reinterpret_cast<f32x4*>(fs + 64 + 4 * r) = Z;
             asm volatile("" ::: "memory"); __builtin_amdgcn_wave_barrier();
             const f32x4 wv = *reinterpret_cast<const f32x4*>(fs + 64 + 4 * r);
             asm volatile("" ::: "memory"); __builtin_amdgcn_wave_barrier();
             const float w0 = wv[0], w1 = wv[1], w2 = wv[2], w3 = wv[3];
             const float zb = g == 0 ? w0 : (g == 1 ? w1 : (g == 2 ? w2 : w3));
-#else
-            *reinterpret_cast<f32x4*>(fs + 256 + 64 * g + 4 * r) = Z;      // (lane rows g != k store what they hold: nobody reads it)
-            asm volatile("" ::: "memory"); __builtin_amdgcn_wave_barrier();
-            const float zb = fs[256 + 64 * k + 4 * r + g];
-            asm volatile("" ::: "memory"); __builtin_amdgcn_wave_barrier();
-#endif
             Tn = mfma_(xg, zb, Tn);
         }
     }
@@ -387,7 +373,7 @@ __device__ __forceinline__ void gp_reg_body(const GpMfmaArgs& a, const Ctx& cx, 
             // registers per product.  So the blocks not yet eliminated are kept NEGATED (Un = -A): the trailing update becomes
             // Un[I][J] += R[K][I]^T R[K][J] with both operands as they are, and every other product of the step takes the one
             // negated operand Vn = -L_KK^-T.
-            factor16<(NB <= 2)>(U[uidx(NB, K, K)], Zd[K], dprod, nId, r, g, fsc, nv - 16 * K);
+            factor16<(NB <= 2)>(U[uidx(NB, K, K)], Zd[K], dprod, nId, r, g, fsc, nv - 16 * K);     // (fsc aliases tsc: GPR_SCR)
             SCHED_FENCE();
             // -L_KK^-T: the block transposed through 1.25 KB of LDS (4 dword writes + 4 dword reads, the conflict-free skewed
             // stride-17 layout of mlp_fused.hip's f_turn) instead of a product with the -identity block (4 MFMAs = 128 of the
@@ -396,7 +382,7 @@ __device__ __forceinline__ void gp_reg_body(const GpMfmaArgs& a, const Ctx& cx, 
             if constexpr (NB > 1) {                             // (one block: no panel and no off-diagonal block of L^-1 reads it)
                 const int twr = 68 * g + 12 * (g & 1) + 32 * (g >> 1) + r, trd = 17 * r + 12 * ((r >> 2) & 1) + 32 * (r >> 3) + 4 * g;
 #pragma unroll
-                for (int s = 0; s < 4; ++s) tsc[twr + 17 * s] = -Zd[K][s];
+                for (int s = 0; s < 4; ++s) tsc[twr + 17 * s] = -Zd[K][s];            // (tsc aliases fsc: GPR_SCR)
                 WSYNC();
 #pragma unroll
                 for (int q = 0; q < 4; ++q) Vn[q] = tsc[trd + q];
@@ -474,7 +460,7 @@ __device__ __forceinline__ void gp_reg_body(const GpMfmaArgs& a, const Ctx& cx, 
         const int twr = 68 * g + 12 * (g & 1) + 32 * (g >> 1) + r, trd = 17 * r + 12 * ((r >> 2) & 1) + 32 * (r >> 3) + 4 * g;
         auto turn = [&](f32x4& X) {
 #pragma unroll
-            for (int s = 0; s < 4; ++s) tsc[twr + 17 * s] = X[s];
+            for (int s = 0; s < 4; ++s) tsc[twr + 17 * s] = X[s];                // (tsc aliases fsc: GPR_SCR)
             WSYNC();
 #pragma unroll
             for (int q = 0; q < 4; ++q) X[q] = tsc[trd + q];
@@ -613,7 +599,7 @@ __device__ __forceinline__ void gp_reg_body(const GpMfmaArgs& a, const Ctx& cx, 
                 if (I != J) {                                  // ... and as block (J, I): the transpose
                     f32x4 Wt;
 #pragma unroll
-                    for (int s = 0; s < 4; ++s) tsc[twr + 17 * s] = Wb[s];
+                    for (int s = 0; s < 4; ++s) tsc[twr + 17 * s] = Wb[s];      // (tsc aliases fsc: GPR_SCR)
                     WSYNC();
 #pragma unroll
                     for (int q = 0; q < 4; ++q) Wt[q] = tsc[trd + q];

@@ -375,7 +375,7 @@ static int max_n_for(int want_grad) {
 
 using namespace pacoh;
 
-// MFMA-blocked fp32 path for n <= 128 (gp_mfma.hip); PACOH_DISABLE_MFMA=1 forces the general LDS kernel
+// MFMA-blocked fp32 path for n <= 128 (gp_mfma.hip)
 namespace pacoh {
 struct GpMfmaArgs {
     const float* z; int z_div;
@@ -399,13 +399,9 @@ struct GpPredArgs {            // (same struct as in gp_reg_body.h)
 };
 int gp_reg_predict_try(const GpMfmaArgs& a, const GpPredArgs& pa, hipStream_t s);      // ... its predictive form (n <= 64, no covariance)
 }
-static bool mfma_enabled() {
-    const bool on = g_sw.mfma;
-    return on;
-}
 static int try_mfma(const GpArgs<float>& a, bool bwd, hipStream_t s) {
     if (a.kind != PACOH_KERNEL_RBF) return 1;                  // (the register- / LDS-resident MFMA kernels evaluate the RBF family only)
-    if (!mfma_enabled() || a.n > 128 || a.B <= 0 || a.P <= 0 || a.f <= 0 || a.f > PACOH_MAX_FEATURES ||
+    if (a.n > 128 || a.B <= 0 || a.P <= 0 || a.f <= 0 || a.f > PACOH_MAX_FEATURES ||
         a.z_div <= 0 || a.y_div <= 0 || !a.z || !a.y || !a.ls || !a.noise || (a.mean_mode != PACOH_MEAN_ZERO && !a.mean))
         return 1;
     GpMfmaArgs m = {a.z, a.z_div, a.mean, a.mean_mode, a.y, a.y_div, a.ls, a.os, a.noise, a.n_valid, a.g_lml,
@@ -492,7 +488,7 @@ extern "C" int pacoh_gp_predict(const void* z_ctx, int z_div, const void* mean_c
         a.mu = (float*)mu; a.var = (float*)var; a.V_out = cov ? (float*)workspace : nullptr; a.m = m; a.info = info;
         // marginal predictive of an RBF-family GP at n <= 128, f <= 4: the register-resident MFMA kernel (round 5)
         rc = 1;
-        if (a.kind == PACOH_KERNEL_RBF && mfma_enabled() && a.n <= 128 && a.f <= 4 && info && B > 0 && P > 0 && z_div > 0 && y_div > 0 && z_ctx && y &&
+        if (a.kind == PACOH_KERNEL_RBF && a.n <= 128 && a.f <= 4 && info && B > 0 && P > 0 && z_div > 0 && y_div > 0 && z_ctx && y &&
             lengthscale && noise && (mean_mode == PACOH_MEAN_ZERO || mean_ctx)) {
             GpMfmaArgs ma = {a.z, a.z_div, a.mean, a.mean_mode, a.y, a.y_div, a.ls, a.os, a.noise, a.n_valid, nullptr,
                              nullptr, info, nullptr, nullptr, nullptr, nullptr, nullptr, a.B, a.P, a.n, a.f};

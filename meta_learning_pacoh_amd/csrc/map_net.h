@@ -14,10 +14,7 @@
 namespace pacoh {
 namespace {
 
-#ifndef PACOH_MP_NT
-#define PACOH_MP_NT 1024
-#endif
-constexpr int MP_NT = PACOH_MP_NT;   // threads per workgroup of the persistent kernel (16 waves: up to 16 tasks per iteration, one wave each)
+constexpr int MP_NT = 1024;          // threads per workgroup of the persistent kernel (16 waves: up to 16 tasks per iteration, one wave each)
 constexpr int MP_MAXL = 5;           // up to 4 hidden layers + the output layer
 constexpr int MP_MAXQ = 9;           // quads per row: in <= 32 -> S <= 36
 constexpr int MP_LDS_BYTES = 158 * 1024;   // dynamic LDS the plan may use (the CU has 160 KB; the kernel's static LDS is < 1 KB)

@@ -15,20 +15,11 @@ namespace pacoh {
 void read_switches(Switches& s) {
     auto off0 = [](const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); };     // on unless NAME=0
     auto num = [](const char* name, int dflt) { const char* e = getenv(name); return (e && e[0]) ? atoi(e) : dflt; };
-    s.chol_ll = off0("PACOH_CHOL_LL"); s.trtri_ll = off0("PACOH_TRTRI_LL"); s.retry_fused = off0("PACOH_RETRY_FUSED");
-    s.gemm_tile = off0("PACOH_GEMM_TILE"); s.trtri_blocked = off0("PACOH_TRTRI_BLOCKED"); s.chol_blocked = off0("PACOH_CHOL_BLOCKED");
-    s.grad_mfma = off0("PACOH_GRAD_MFMA"); s.grad_mfma_f32 = off0("PACOH_GRAD_MFMA_F32"); s.gram_mfma = off0("PACOH_GRAM_MFMA");
-    s.dense_pad = off0("PACOH_DENSE_PAD");
-    s.mfma = num("PACOH_DISABLE_MFMA", 0) != 1;
+    s.chol_ll = off0("PACOH_CHOL_LL"); s.trtri_blocked = off0("PACOH_TRTRI_BLOCKED"); s.chol_blocked = off0("PACOH_CHOL_BLOCKED");
     s.gp8 = off0("PACOH_GP8");
-    s.gp_reg = off0("PACOH_GP_REG"); s.gp_reg_predict = off0("PACOH_GP_REG_PREDICT"); s.gp_reg_max_n = num("PACOH_GP_REG_MAX_N", 128);
-    s.fused_mlp = num("PACOH_DISABLE_FUSED_MLP", 0) == 0;
     const char* e = getenv("PACOH_MLP_PATH");
     s.mlp_path = !e ? 0 : (!strcmp(e, "mfma") ? 1 : (!strcmp(e, "layers") ? 3 : 0));
-    s.mlp_stash = num("PACOH_MLP_STASH", -1);
-    s.lds_pad_gp = num("PACOH_LDS_PAD_GP", -1); s.lds_pad_mlp = num("PACOH_LDS_PAD_MLP", -1);
     s.mt_nt = num("PACOH_MT_NT", 0);
-    s.fused_bwd_pb = num("PACOH_FUSED_BWD_PB", 0); s.fused_fwd_pb = num("PACOH_FUSED_FWD_PB", 0); s.fused_fwd_tpw = num("PACOH_FUSED_FWD_TPW", 0);
 }
 Switches g_sw = []() { Switches s; read_switches(s); return s; }();
 

@@ -559,8 +559,7 @@ __global__ void __launch_bounds__(256) fused_reduce_slab_kernel(SlabReduce s0, S
 // ---- host side ----------------------------------------------------------------------------------------------------
 
 bool mlp_fused_applicable(int d_in, const int32_t* hidden, int n_hidden, int d_out) {
-    const bool on = g_sw.fused_mlp;
-    if (!on || n_hidden < 1 || n_hidden > FMAXNH || d_in < 1 || d_in > 4 || d_out < 1 || d_out > 2) return false;
+    if (n_hidden < 1 || n_hidden > FMAXNH || d_in < 1 || d_in > 4 || d_out < 1 || d_out > 2) return false;
     for (int l = 0; l < n_hidden; ++l) if (hidden[l] < 1 || hidden[l] > 32) return false;
     return true;
 }
@@ -574,10 +573,8 @@ static int fused_dnet(int d_in, const int32_t* hidden, int n_hidden, int d_out) 
 // point blocks (of 16) per tile.  Small launches -- fewer 64-point tiles than the chip has wave slots, e.g. PACOH-MAP's 256 tasks x 32
 // points x one parameter row -- are one tile per wave either way and pure latency: 32-point tiles halve that latency
 static bool fused_small(int R, int P, int nets) { return (long)((R + 63) / 64) * P * nets <= 512; }
-static int fused_bwd_pb(int n_hidden, int R, int P, int nets) {
-    return g_sw.fused_bwd_pb > 0 ? g_sw.fused_bwd_pb : ((n_hidden <= 2 && !fused_small(R, P, nets)) ? 4 : 2);
-}
-static int fused_fwd_pb(int, int R, int P, int nets) { return g_sw.fused_fwd_pb > 0 ? g_sw.fused_fwd_pb : (fused_small(R, P, nets) ? 2 : 4); }
+static int fused_bwd_pb(int n_hidden, int R, int P, int nets) { return (n_hidden <= 2 && !fused_small(R, P, nets)) ? 4 : 2; }
+static int fused_fwd_pb(int R, int P, int nets) { return fused_small(R, P, nets) ? 2 : 4; }
 
 // resident workgroups of a kernel on the whole chip (occupancy query, cached per kernel)
 template <typename K> static int resident_wgs(K kern) {
@@ -607,14 +604,9 @@ static int fused_chunks(int R, int P, int nets, int tp, int resident, double ove
 
 // Hidden layers (counted from the top) whose activations the forward parks in HBM for the backward.  Default: all but the first
 // (whose recomputation is one MFMA per block on d_in <= 4 inputs) -- measured at the cfg #3 shape (1024 tasks x 20 particles x
-// 64 points, both networks; tools/mlp_time.py): 2 x 32: forward 88 -> 100 us, backward 207 -> 171 us (stashing the first layer too:
+// 64 points, both networks; profiles/r03_mlp_stash_ab.txt): 2 x 32: forward 88 -> 100 us, backward 207 -> 171 us (stashing the first layer too:
 // forward 141 us); 4 x 32: forward + backward 801 us without, 694 / 665 / 641 / 663 us with 1 / 2 / 3 / 4 layers stashed.
-// PACOH_MLP_STASH=k stashes k layers (0: recompute everything, as rounds 1-2 did).
-static int fused_n_stash(int n_hidden) {
-    const int want = g_sw.mlp_stash;                               // (PACOH_MLP_STASH, switches.h; -1: the dispatcher's choice)
-    if (want < 0) return n_hidden > 1 ? n_hidden - 1 : 0;
-    return want > n_hidden ? n_hidden : want;
-}
+static int fused_n_stash(int n_hidden) { return n_hidden > 1 ? n_hidden - 1 : 0; }
 static int fused_nblk(int B, int P, int n) { return 4 * (int)(((long)(B / P) * n + 63) / 64); }
 
 // bytes of activation stash for `nets` networks (0: this build / shape keeps none)
@@ -630,11 +622,7 @@ static void fused_fill(FusedArgs& a, const void* x, int x_div, const void* theta
     a.n_stash = stash ? fused_n_stash(n_hidden) : 0;
     a.nblk = fused_nblk(B, P, n);
     const size_t per_net = (size_t)P * a.nblk * a.n_stash * 2 * 256;
-#ifdef PACOH_EXP_STASH_NETS      // experiment build (VERDICT r3 #4a): only the first PACOH_EXP_STASH_NETS networks use the stash, the others recompute
-    for (int k = 0; k < 2; ++k) a.net[k].stash = (a.n_stash > 0 && k < nets && k < PACOH_EXP_STASH_NETS) ? (float*)stash + k * per_net : nullptr;
-#else
     for (int k = 0; k < 2; ++k) a.net[k].stash = (a.n_stash > 0 && k < nets) ? (float*)stash + k * per_net : nullptr;
-#endif
 }
 
 constexpr int BWD_MINW = 3;      // NH <= 2, 64-point tiles: three waves per SIMD (168 registers; forcing 128 spills)
@@ -658,19 +646,16 @@ int mlp_fused_fwd(const void* x, int x_div, const void* theta, long theta_stride
     FusedArgs a = {};
     fused_fill(a, x, x_div, theta, theta_stride, P, d_in, hidden, n_hidden, B, n, stash, nets);
     for (int k = 0; k < nets; ++k) { a.net[k].theta_off = off[k]; a.net[k].out = (float*)out[k]; a.net[k].d_out = d_out[k]; }
-    const int pb = fused_fwd_pb(n_hidden, a.R, P, nets) == 2 ? 2 : 4;
+    const int pb = fused_fwd_pb(a.R, P, nets);
     const int tiles = (a.R + 16 * pb - 1) / (16 * pb);
     // tiles per workgroup (a wave takes every 4th): 16 at cfg #3 (4 / 8 / 16 / 32: 109 / 100 / 95 / 94 us); small batches -- the 1/8
     // strong-scaling shard -- want fewer, or a SIMD holds two four-tile waves while its neighbour idles: the count that minimises
     // (waves per SIMD) x (tiles per wave + half a tile of fixed cost), larger counts winning ties
-    a.tiles_per_wg = g_sw.fused_fwd_tpw;
-    if (a.tiles_per_wg <= 0) {
-        double best = 1e30;
-        for (int tpw = 4; tpw <= 32; tpw *= 2) {
-            const long waves = (long)((tiles + tpw - 1) / tpw) * P * nets * 4;
-            const double cost = (double)((waves + 1023) / 1024) * (tpw / 4 + 0.5);
-            if (cost <= best * 1.02 || tpw == 4) { if (cost < best) best = cost; a.tiles_per_wg = tpw; }
-        }
+    double best = 1e30;
+    for (int tpw = 4; tpw <= 32; tpw *= 2) {
+        const long waves = (long)((tiles + tpw - 1) / tpw) * P * nets * 4;
+        const double cost = (double)((waves + 1023) / 1024) * (tpw / 4 + 0.5);
+        if (cost <= best * 1.02 || tpw == 4) { if (cost < best) best = cost; a.tiles_per_wg = tpw; }
     }
     const int wgs = (tiles + a.tiles_per_wg - 1) / a.tiles_per_wg;
     // The tail slice of the grid has wgs x P workgroups for the P (P + 1) / 2 particle pairs (+ the snapshot rows).  A thin slice walks
@@ -680,8 +665,7 @@ int mlp_fused_fwd(const void* x, int x_div, const void* theta, long theta_stride
     if (tail && (long)wgs * P * 2 < (long)tail->P * (tail->P + 1) / 2) tail = nullptr;
     if (tail_taken) *tail_taken = tail != nullptr;
     if (tail) { a.tail_z = nets; a.sv = *tail; }
-    const unsigned pad = g_sw.lds_pad_mlp > 0 ? (unsigned)g_sw.lds_pad_mlp : 0u;
-#define PACOH_LAUNCH_FWD(K) hipLaunchKernelGGL((K), dim3(wgs, P, nets + (tail ? 1 : 0)), dim3(256), pad, s, a)
+#define PACOH_LAUNCH_FWD(K) hipLaunchKernelGGL((K), dim3(wgs, P, nets + (tail ? 1 : 0)), dim3(256), 0, s, a)
     if (pb == 4) {
         if (n_hidden == 1) PACOH_LAUNCH_FWD((mlp_fused_fwd_kernel<1, 4, 4>)); else if (n_hidden == 2) PACOH_LAUNCH_FWD((mlp_fused_fwd_kernel<2, 4, 4>));
         else if (n_hidden == 3) PACOH_LAUNCH_FWD((mlp_fused_fwd_kernel<3, 4, 4>)); else PACOH_LAUNCH_FWD((mlp_fused_fwd_kernel<4, 4, 4>));
@@ -697,7 +681,7 @@ struct FusedBwdPlan { int pb, chunks, tiles_per_wg; };
 
 static FusedBwdPlan fused_bwd_plan(int R, int P, int nets, int n_hidden) {
     FusedBwdPlan pl;
-    pl.pb = fused_bwd_pb(n_hidden, R, P, nets) == 2 ? 2 : 4;
+    pl.pb = fused_bwd_pb(n_hidden, R, P, nets);
     static int resident[FMAXNH + 1][2] = {};
     int& res = resident[n_hidden][pl.pb == 4];
     if (res == 0) {
@@ -744,8 +728,7 @@ int mlp_fused_bwd(const void* x, int x_div, const void* theta, long theta_stride
     if (bw_here) { a.bw_d2 = tail->sv_d2; a.bw_P = tail->sv_P; a.bw_out = tail->sv_bw; rtail.sv_bw = nullptr; }
     if (adv_here) a.adv_counter = const_cast<long*>(tail->nx.counter);
     if (bw_here || adv_here) a.tail_z = nets;
-    const unsigned pad = g_sw.lds_pad_mlp > 0 ? (unsigned)g_sw.lds_pad_mlp : 0u;
-#define PACOH_LAUNCH_BWD(K) hipLaunchKernelGGL(K, dim3(pl.chunks, P, nets + ((bw_here || adv_here) ? 1 : 0)), dim3(256), pad, s, a)
+#define PACOH_LAUNCH_BWD(K) hipLaunchKernelGGL(K, dim3(pl.chunks, P, nets + ((bw_here || adv_here) ? 1 : 0)), dim3(256), 0, s, a)
     PACOH_FUSED_DISPATCH(mlp_fused_bwd_kernel, n_hidden, pl.pb, PACOH_LAUNCH_BWD);
 #undef PACOH_LAUNCH_BWD
     const long tot = (long)P * wmax;

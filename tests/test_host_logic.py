@@ -335,3 +335,27 @@ def test_bench_dump_outputs_dtypes_and_size_cap(tmp_path):
     assert np.all(np.diff(got['big']) > 0) and np.array_equal(got['big'], np.unique(got['big']))       # distinct elements, in order
     assert np.array_equal(got['big'], np.load(str(tmp_path / 'b' / 'big.npy')))                        # the same sample every time
     assert sum(os.path.getsize(str(tmp_path / 'a' / (k + '.npy'))) for k in arrays) <= bench.DUMP_BYTES
+
+
+def test_design_switch_table_matches_the_code():
+    """DESIGN.md section 8 lists exactly the PACOH_* environment names the code reads or sets and the -D flags the kernel sources test"""
+    import glob
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def text(*patterns):
+        return ''.join(open(p).read() for pat in patterns for p in sorted(glob.glob(os.path.join(root, pat))))
+    design = open(os.path.join(root, 'DESIGN.md')).read()
+    sec8 = design[design.index('\n## 8. '):]
+    sec8 = sec8[:sec8.find('\n## ', 1)] if '\n## ' in sec8[1:] else sec8
+    listed = ' '.join(ln.split('|')[1] for ln in sec8.splitlines() if ln.startswith('| '))          # first column of the table
+    listed_env = set(re.findall(r'`(PACOH_[A-Z0-9_]+)', listed))
+    listed_flags = set(re.findall(r'`-D(PACOH_[A-Z0-9_]+)', listed))
+    native = text('meta_learning_pacoh_amd/csrc/*', 'tests/asan/abi_shim.cpp')
+    py = text('meta_learning_pacoh_amd/*.py', 'bench.py', 'tools/*.py')
+    code_env = set(re.findall(r'\b(?:getenv|off0|num)\("(PACOH_[A-Z0-9_]+)"', native))
+    code_env |= set(re.findall(r'\benv(?:iron)?\s*(?:\[|\.(?:get|pop|setdefault)\()\s*[\'"](PACOH_[A-Z0-9_]+)', py))
+    code_env |= set(re.findall(r'\b(PACOH_[A-Z0-9_]+)=', text('tools/*.sh')))
+    code_flags = set(re.findall(r'#\s*if(?:n?def\s+|.*defined\s*\(?\s*)(PACOH_[A-Z0-9_]+)', text('meta_learning_pacoh_amd/csrc/*')))
+    assert listed_env == code_env, 'only in DESIGN: %s; only in the code: %s' % (sorted(listed_env - code_env), sorted(code_env - listed_env))
+    assert listed_flags == code_flags, 'only in DESIGN: %s; only in csrc: %s' % (sorted(listed_flags - code_flags), sorted(code_flags - listed_flags))

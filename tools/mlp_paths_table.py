@@ -19,8 +19,6 @@ def applicable(path, dtype, d_in, hidden, d_out):
         return f32 and 1 <= nh <= 4 and d_in <= 4 and d_out <= 2 and all(h <= 32 for h in hidden)
     if path == 'mfma':
         return f32 and 1 <= nh <= 2 and d_in <= 16 and d_out <= 8 and all(h <= 32 for h in hidden)
-    if path == 'valu':
-        return nh <= 3 and d_in <= 16 and d_out <= 8 and all(h <= 64 for h in hidden)
     return True
 
 
@@ -38,7 +36,7 @@ def timeit(fn, reps=30):
 
 
 def main():
-    paths = [p for p in ('fused', 'mfma', 'valu', 'layers') if p != 'valu' or os.environ.get('PACOH_HAVE_VALU') == '1']
+    paths = ['fused', 'mfma', 'layers']
     print('%-44s %-5s %6s | %s | fastest | the only path' % ('shape (P, T, n, d_in, hidden, d_out)', 'dtype', 'tasks', ' '.join('%9s' % p for p in paths)))
     wins = {p: 0 for p in paths}
     sole = {p: 0 for p in paths}

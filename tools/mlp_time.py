@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """A/B timing of the per-particle MLP kernels at the cfg #3 shape (1024 tasks x 20 particles, n = 64, d = 4):
-mean + kernel-feature network, forward and backward, per implementation (PACOH_MLP_PATH) and tile shape.
+mean + kernel-feature network, forward and backward, per implementation (PACOH_MLP_PATH).
     python tools/mlp_time.py [--layers 32,32] [--reps 50]"""
 import argparse
 import os
@@ -33,7 +33,6 @@ def main():
     ap.add_argument('--particles', type=int, default=20)
     ap.add_argument('--n', type=int, default=64)
     ap.add_argument('--d', type=int, default=4)
-    ap.add_argument('--quick', action='store_true', help='default tile shapes only')
     args = ap.parse_args()
     hidden = [int(v) for v in args.layers.split(',')]
     T, P, n, d = args.tasks, args.particles, args.n, args.d
@@ -60,13 +59,6 @@ def main():
     def pair_bwd():
         ws['p'] = L.mlp2_bwd(x, P, theta, P, d, hidden, 0, 1, g_m, Dm, 2, g_k, grad, False, B, n, ws.get('p'))
 
-    def stash_pair(fwd_only=False, bwd_only=False):
-        st = ws['stash'] = L.mlp2_stash(x, P, d, hidden, 1, 2, B, n, ws.get('stash'))
-        if not bwd_only:
-            L.mlp2_fwd(x, P, theta, P, d, hidden, 0, 1, Dm, 2, B, n, stash=st)
-        if not fwd_only:
-            ws['p'] = L.mlp2_bwd(x, P, theta, P, d, hidden, 0, 1, g_m, Dm, 2, g_k, grad, False, B, n, ws.get('p'), stash=st)
-
     def two_fwd():
         L.mlp_fwd(x, P, theta, D, P, d, hidden, 1, B, n)
         L.mlp_fwd(x, P, theta[:, Dm:], D, P, d, hidden, 2, B, n)
@@ -75,51 +67,26 @@ def main():
         ws['a'] = L.mlp_bwd(x, P, theta, D, P, d, hidden, 1, g_m, grad, D, False, B, n, ws.get('a'))
         ws['b'] = L.mlp_bwd(x, P, theta[:, Dm:], D, P, d, hidden, 2, g_k, grad[:, Dm:], D, False, B, n, ws.get('b'))
 
-    def setenv(**kw):
-        for k, v in kw.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = str(v)
+    def setpath(path):
+        if path is None:
+            os.environ.pop('PACOH_MLP_PATH', None)
+        else:
+            os.environ['PACOH_MLP_PATH'] = path
         L.reload_env()
 
     rows = []
     for path in (None, 'mfma'):
-        if path == 'mfma' and (len(hidden) > 2 or args.quick):
+        if path == 'mfma' and len(hidden) > 2:
             continue
-        setenv(PACOH_MLP_PATH=path)
-        if path is None and args.quick:
+        setpath(path)
+        ws.clear()
+        if path is None:
             rows.append(('fused fwd pair', timeit(pair_fwd, args.reps)))
             rows.append(('fused bwd pair', timeit(pair_bwd, args.reps)))
-            for ns in range(0, len(hidden) + 1):
-                setenv(PACOH_MLP_STASH=ns)
-                ws.clear()
-                stash_pair()
-                rows.append(('stash %d layer(s): fwd' % ns, timeit(lambda: stash_pair(fwd_only=True), args.reps)))
-                rows.append(('stash %d layer(s): bwd' % ns, timeit(lambda: stash_pair(bwd_only=True), args.reps)))
-                rows.append(('stash %d layer(s): fwd + bwd' % ns, timeit(stash_pair, args.reps)))
-            setenv(PACOH_MLP_STASH=None)
-            ws.clear()
-        elif path is None:
-            for pb in (4, 2):
-                setenv(PACOH_FUSED_FWD_PB=pb)
-                for tpw in (4, 8, 16, 32):
-                    setenv(PACOH_FUSED_FWD_TPW=tpw)
-                    rows.append(('fused fwd pair pb=%d tpw=%d' % (pb, tpw), timeit(pair_fwd, args.reps)))
-            setenv(PACOH_FUSED_FWD_PB=None, PACOH_FUSED_FWD_TPW=None)
-            for pb in (4, 2):
-                setenv(PACOH_FUSED_BWD_PB=pb)
-                ws.clear()
-                rows.append(('fused bwd pair pb=%d' % pb, timeit(pair_bwd, args.reps)))
-            setenv(PACOH_FUSED_BWD_PB=None)
-            ws.clear()
-            rows.append(('fused fwd two calls', timeit(two_fwd, args.reps)))
-            rows.append(('fused bwd two calls', timeit(two_bwd, args.reps)))
-        else:
-            ws.clear()
-            rows.append(('%s fwd two calls' % path, timeit(two_fwd, args.reps)))
-            rows.append(('%s bwd two calls' % path, timeit(two_bwd, args.reps)))
-    setenv(PACOH_MLP_PATH=None)
+        name = path or 'fused'
+        rows.append(('%s fwd two calls' % name, timeit(two_fwd, args.reps)))
+        rows.append(('%s bwd two calls' % name, timeit(two_bwd, args.reps)))
+    setpath(None)
     for name, us in rows:
         print('%-36s %9.1f us' % (name, us))
 
