@@ -360,9 +360,11 @@ def _gp_lml_dense(z, z_div, mean, mean_mode, y, y_div, lengthscale, outputscale,
         d_noise = torch.empty(B, dtype=dt, device=dev)
     # The scratch is O(B n^2).  The entry point itself runs the batch in slabs of whole tasks when it is handed less than the whole
     # batch needs, and pads context sizes with misaligned rows onto the left-looking kernels (round 6: both lived here before): the
-    # binding only bounds the buffer -- DENSE_WS_BYTES, but never less than one task's share
+    # binding only bounds the buffer -- DENSE_WS_BYTES, but never less than one task's share.  Slabs need the task-major layout with
+    # every input per problem or per task (z_div, y_div in {1, P}); any other batch gets the whole buffer, as the entry point rejects
+    # a capped one
     need = lib.pacoh_gp_lml_dense_workspace_bytes(B, n, _kf(f, kernel), code, int(want_grad))
-    if need > DENSE_WS_BYTES and B % P == 0 and B > P:
+    if need > DENSE_WS_BYTES and B % P == 0 and B > P and z_div in (1, P) and y_div in (1, P):
         one = max(1, lib.pacoh_gp_lml_dense_workspace_bytes(P, n, _kf(f, kernel), code, int(want_grad)))
         need = min(need, max(one, DENSE_WS_BYTES // one * one))
     ws = _workspace('lml', need, dev)

@@ -551,12 +551,18 @@ __device__ __forceinline__ void gp_reg_body(const GpMfmaArgs& a, const Ctx& cx, 
 #pragma unroll
             for (int c = 0; c < FP; ++c) zi[c] = zf[(16 * I + 4 * g + s) * FP + c];
             const float Gij = fmaf(ai4[s], aj, -Wb[s]);
-            if (diag) dnz = fmaf(nId[s], Gij, dnz);           // minus the trace part (padding rows: taken out again below)
+            // a padding row's diagonal entry (G_ii = -1, kernel entry 1) stays out of both sums: added and taken out again at the end,
+            // (16 NB - nv) of them swamped the sums of a small task (d_os, d_noise of a one-point task in the eight-block kernel lost
+            // 2.5e-4 relative, 200x what fp32 loses on the same expression).  Only the diagonal tiles (I == J) are masked: every entry
+            // of a padding row or column off the diagonal -- in a diagonal tile or any tile I != J -- still relies on its kernel entry
+            // exp2(-|dz|^2) being an exact zero (the padding points sit far apart), so that M_ij = 0 there
+            const bool live = !diag || 16 * I + 4 * g + s < nv;
+            if (diag && live) dnz = fmaf(nId[s], Gij, dnz);   // minus the trace part
             float q = 0.0f, df[FP];
 #pragma unroll
             for (int c = 0; c < FP; ++c) { df[c] = zi[c] - zc[c]; q = fmaf(df[c], df[c], q); }
             const float M = Gij * __builtin_amdgcn_exp2f(-q);
-            if (HAS_OS) msum += M;
+            if (HAS_OS) msum += live ? M : 0.0f;
 #pragma unroll
             for (int c = 0; c < FP; ++c) colacc[c] = fmaf(M, df[c], colacc[c]);
         }
@@ -718,9 +724,7 @@ __device__ __forceinline__ void gp_reg_body(const GpMfmaArgs& a, const Ctx& cx, 
             if (lane == 0) GPR_LATE(d_ls)[b * f + c] = (INV_KAPPA2 / KAPPA) * gup * sc * kls[c] + bad;
         }
     }
-    // a padding row's diagonal entry is G_ii = (0 - 1) osn exactly, with kernel entry 1: out of both sums again
-    const float padc = (float)(NP - nv) * osn;
-    const float sdos = osn * wave_sum_(msum) + padc, sdnz = padc - osn * wave_sum_(dnz);
+    const float sdos = osn * wave_sum_(msum), sdnz = -osn * wave_sum_(dnz);
     if (lane == 0) {
         float* d_os_p = GPR_LATE(d_os);
         const float inv_os = rcp_(os);

@@ -392,6 +392,36 @@ def test_dense_path_slabs_match_single_pass(L):
         assert (a is None and b is None) or torch.equal(a, b)
 
 
+@pytest.mark.parametrize('dtype', [torch.float32, torch.float64])
+def test_dense_path_budget_with_inputs_shared_by_the_whole_batch(L, monkeypatch, dtype):
+    """a batch the entry point cannot cut into slabs of whole tasks (z_div = y_div = B: one input set for every problem) gets the whole
+    workspace even when it is over DENSE_WS_BYTES -- a capped buffer is PACOH_EINVAL there: same results as without the budget, and
+    the oracle's"""
+    T, P, n, f = 3, 2, 129, 2
+    B = T * P
+    z, mean, y, ls, os_, noise = make_problem(T, P, n, f, dtype, seed=129, noise_lo=0.05)
+    z, y = z[:1].contiguous(), y[:1].contiguous()
+    gl = torch.rand(B, dtype=dtype) + 0.5
+    d = [t.to(DEV) for t in (z, mean, y, ls, os_, noise, gl)]
+    call = lambda: L.gp_lml_fwdbwd(d[0], B, d[1], L.MEAN_VECTOR, d[2], B, d[3], d[4], d[5], B, P, g_lml=d[6])
+    full = call()
+    need = L.load_library().pacoh_gp_lml_dense_workspace_bytes(B, n, f, L.dtype_code(z), 1)
+    monkeypatch.setattr(L, 'DENSE_WS_BYTES', need // 4)
+    capped = call()
+    for a, b in zip(full, capped):
+        assert (a is None and b is None) or torch.equal(a, b)
+    lml, d_z, d_mean, d_ls, d_os, d_noise, info = capped
+    assert int(info.abs().max()) == 0
+    leaves = [t.double().clone().requires_grad_(True) for t in (z[0].expand(B, n, f), mean, ls, os_, noise)]
+    ref = oracle_mll(leaves[0], leaves[1], y[0].double().expand(T, n), leaves[2], leaves[3], leaves[4], T, P, True)
+    (ref * gl.double()).sum().backward()
+    tol_l, tol_g = (1e-4, 5e-4) if dtype == torch.float32 else (1e-9, 1e-7)
+    assert maxrel(lml, ref) < tol_l
+    assert relerr(d_z, leaves[0].grad) < tol_g and relerr(d_mean, leaves[1].grad) < tol_g
+    assert relerr(d_ls.reshape(T, P, f).sum(0), leaves[2].grad) < tol_g
+    assert relerr(d_os.reshape(T, P).sum(0), leaves[3].grad) < tol_g and relerr(d_noise.reshape(T, P).sum(0), leaves[4].grad) < tol_g
+
+
 @pytest.mark.parametrize('dtype,n', [(torch.float32, 509), (torch.float64, 255), (torch.float32, 641)])
 def test_raw_c_abi_call_pads_and_slabs_by_itself(L, dtype, n):
     """a host that binds pacoh_gp_lml_dense directly gets what the Python binding gives -- a

@@ -64,7 +64,7 @@ def test_lml_fwdbwd_random_shapes(L, dtype, seed):
                           n_valid=d(sizes.to(torch.int32)) if c['ragged'] else None, g_lml=d(glq), want_dz=not c['shared_z'])
     lml, d_z, d_mean, d_ls, d_os, d_noise, info = [None if o is None else o.cpu() for o in out]
     assert int(info.abs().max()) == 0, c
-    ltol, gtol = (2e-4, 1e-2) if dtype == torch.float32 else (1e-9, 1e-7)
+    ltol, gtol = (1e-5, 1e-3) if dtype == torch.float32 else (1e-9, 1e-7)     # (fp32 measured over the 40 draws: LML 8.4e-7, gradients 2.4e-4)
     ref_lml = torch.zeros(B, dtype=torch.float64)
     ref = dict(z=torch.zeros(B, n, f, dtype=torch.float64), mean=torch.zeros(B, n, dtype=torch.float64), const=torch.zeros(B, dtype=torch.float64),
                ls=torch.zeros(B, f, dtype=torch.float64), os=torch.zeros(B, dtype=torch.float64), noise=torch.zeros(B, dtype=torch.float64))

@@ -22,7 +22,7 @@ def L():
 
 
 DEV = 'cuda'
-TOL = {torch.float32: 2e-3, torch.float64: 1e-9}       # asserted (bars: 1e-2 / 1e-4)
+TOL = {torch.float32: 2e-5, torch.float64: 1e-9}       # asserted (bars: 1e-2 / 1e-4); fp32: LML and L measured <= 1.4e-6 (profiles/small_fp32_errors.txt)
 
 
 def relerr(a, b):
@@ -142,7 +142,7 @@ def test_lml_fwd(L, dtype, case):
     L0 = torch.linalg.cholesky(K0)
     assert relerr(Lf[0], L0) < TOL[dtype]
     a0 = torch.cholesky_solve((y[0] - mean[0]).double().unsqueeze(-1), L0).squeeze(-1)
-    assert relerr(alpha[0], a0) < (5e-2 if dtype == torch.float32 else 1e-8)
+    assert relerr(alpha[0], a0) < (1e-5 if dtype == torch.float32 else 1e-8)           # (fp32: measured 1.0e-6)
 
 
 def test_lml_mean_modes_and_unit_outputscale(L):
@@ -173,7 +173,7 @@ def test_lml_fwdbwd(L, dtype, case):
     lml, d_z, d_mean, d_ls, d_os, d_noise, info = out
     assert int(info.abs().max()) == 0
     assert maxrel(lml, ref) < TOL[dtype]
-    gtol = 1e-2 if dtype == torch.float32 else 1e-8
+    gtol = 5e-5 if dtype == torch.float32 else 1e-8      # (fp32: measured <= 3.4e-6 over these cases, summed and per problem)
     if pez:
         assert relerr(d_z, leaves[0].grad) < gtol
     assert relerr(d_mean, leaves[1].grad) < gtol
@@ -181,6 +181,14 @@ def test_lml_fwdbwd(L, dtype, case):
     assert relerr(d_ls.reshape(T, P, f).sum(0), leaves[2].grad) < gtol
     assert relerr(d_os.reshape(T, P).sum(0), leaves[3].grad) < gtol
     assert relerr(d_noise.reshape(T, P).sum(0), leaves[4].grad) < gtol
+    # ... and problem by problem (no sum over tasks): (d_ls, d_os, d_noise)[b] against the gradient of problem b's own copy of its row
+    hyp = [t.double().unsqueeze(0).expand(T, P, *t.shape[1:]).reshape(T * P, *t.shape[1:]).clone().requires_grad_(True) for t in (ls, os_, noise)]
+    zz = z.double() if pez else z.double().unsqueeze(1).expand(T, P, n, f).reshape(T * P, n, f)
+    ref_b = O.gp_mll(zz, mean.double(), y.double().unsqueeze(1).expand(T, P, n).reshape(T * P, n), hyp[0].unsqueeze(1), hyp[1], hyp[2])
+    (ref_b * gl.double()).sum().backward()
+    for b in range(T * P):
+        got = torch.cat([d_ls[b].cpu(), d_os[b:b + 1].cpu(), d_noise[b:b + 1].cpu()])
+        assert relerr(got, torch.cat([hyp[0].grad[b], hyp[1].grad[b:b + 1], hyp[2].grad[b:b + 1]])) < gtol, b
 
 
 def test_lml_const_mean_grad(L):
