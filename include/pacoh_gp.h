@@ -57,9 +57,22 @@ extern "C" {
  *                        suite hands to the single-task learner (tests/test_GPR.py:95-101; GPR_mll.py:66-78 takes any Kernel
  *                        object): `lengthscale[p, 0..f)` all hold the period length; d_lengthscale[b, c] comes back per
  *                        dimension and its sum over c is the gradient of the period.  General (LDS-resident / HBM-resident)
- *                        kernels only: not a hot path. */
+ *                        kernels only: not a hot path.
+ *   PACOH_KERNEL_MATERN12 / _MATERN32 / _MATERN52   gpytorch.kernels.MaternKernel(nu = 1/2, 3/2, 5/2) with ARD lengthscales: with
+ *                        s = |(x - x') / lengthscale| (per-dimension lengthscale[p, c], like RBF),
+ *                          nu = 1/2   k = os * exp(-s)
+ *                          nu = 3/2   k = os * (1 + sqrt(3) s) exp(-sqrt(3) s)
+ *                          nu = 5/2   k = os * (1 + sqrt(5) s + 5/3 s^2) exp(-sqrt(5) s)
+ *                        The nu = 1/2 gradient is singular at s = 0: coincident points contribute none (gpytorch's clamped
+ *                        distance).  fp32 with n <= 128 and f <= 4 runs on the register-resident kernels like RBF; every other
+ *                        shape and fp64 on the general kernels.  Family code 2 is unassigned.
+ * pacoh_hyper_fwd / _bwd and pacoh_step_begin treat only COSINE as tied: the Matérn families have f raw scales, like RBF.  The
+ * task-fused and persistent entry points (pacoh_svgd_task_*, pacoh_map_persist*, pacoh_map_task_*) evaluate ARD-RBF only. */
 #define PACOH_KERNEL_RBF 0
 #define PACOH_KERNEL_COSINE 1
+#define PACOH_KERNEL_MATERN12 3
+#define PACOH_KERNEL_MATERN32 4
+#define PACOH_KERNEL_MATERN52 5
 #define PACOH_KERNEL_SHIFT 8
 #define PACOH_MLP_MAX_HIDDEN_LAYERS 63   /* per-particle MLP: any layer_sizes up to this depth ...          */
 #define PACOH_MLP_MAX_WIDTH 65536        /* ... and this width (the reference has no limit: models.py:328-349) */

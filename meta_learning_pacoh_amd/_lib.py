@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get('PACOH_LIB') or os.path.join(_HERE, 'lib', 'libpacoh_g
 F32, F64 = 0, 1
 MEAN_ZERO, MEAN_VECTOR, MEAN_CONST = 0, 1, 2
 KERNEL_RBF, KERNEL_COSINE, KERNEL_SHIFT = 0, 1, 8          # PACOH_KERNEL_* (pacoh_gp.h): the family rides in the bits above f
+KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52 = 3, 4, 5   # gpytorch MaternKernel, nu = 1/2, 3/2, 5/2 (ARD, like RBF)
 
 
 def _kf(f, kernel):

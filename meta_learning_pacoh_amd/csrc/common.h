@@ -72,20 +72,50 @@ template <> __device__ __forceinline__ float rbf_exp<float>(float x) {
 // pacoh_gp.h): f_arg = f | (kernel << PACOH_KERNEL_SHIFT).  In scaled coordinates u = z / lengthscale, with s2 = |u_i - u_j|^2:
 //   RBF     k / os = exp(-s2 / 2)          -(d k / d u_ic) / ((u_i - u_j)_c os) = the same value
 //   COSINE  k / os = cos(pi sqrt(s2))      ... = pi sin(pi s) / s   (-> pi^2 for s -> 0)        [gpytorch.kernels.CosineKernel]
+//   MATERN12  k / os = e^-s                ... = e^-s / s, 0 at s = 0 (gpytorch clamps s2 at 1e-30: no gradient there)
+//   MATERN32  k / os = (1 + a) e^-a        ... = 3 e^-a,                 a = sqrt(3) s   [gpytorch.kernels.MaternKernel, nu = 3/2]
+//   MATERN52  k / os = (1 + a + a^2/3) e^-a ... = 5/3 (1 + a) e^-a,      a = sqrt(5) s   [nu = 5/2]
 // kern_eval returns both: every gradient of the LML is a contraction with one of the two (d/d outputscale with the first, d/d z
 // and d/d lengthscale with the second), so the kernels that evaluate the RBF family evaluate any family given this pair.
 __host__ __device__ inline int kernel_of(int f_arg) { return f_arg >> PACOH_KERNEL_SHIFT; }
 __host__ __device__ inline int features_of(int f_arg) { return f_arg & ((1 << PACOH_KERNEL_SHIFT) - 1); }
+// the kernel families the GP entry points evaluate (code 2 is unassigned)
+__host__ __device__ inline bool family_known(int kind) {
+    return kind == PACOH_KERNEL_RBF || kind == PACOH_KERNEL_COSINE || (kind >= PACOH_KERNEL_MATERN12 && kind <= PACOH_KERNEL_MATERN52);
+}
+__host__ __device__ inline bool family_matern(int kind) { return kind >= PACOH_KERNEL_MATERN12 && kind <= PACOH_KERNEL_MATERN52; }
+// the families with ONE raw scale shared by all f input dimensions (the `tie` of the hyper-parameter kernels): cosine's period.
+// RBF and Matern have ARD lengthscales, one raw scale per dimension.
+__host__ __device__ inline int ties_scale(int f_arg) { return kernel_of(f_arg) == PACOH_KERNEL_COSINE; }
 template <typename T> __device__ __forceinline__ void sincospi_t(T x, T* s, T* c);
 template <> __device__ __forceinline__ void sincospi_t<float>(float x, float* s, float* c) { sincospif(x, s, c); }
 template <> __device__ __forceinline__ void sincospi_t<double>(double x, double* s, double* c) { sincospi(x, s, c); }
 template <typename T> __device__ __forceinline__ void kern_eval(int kind, T s2, T& kv, T& kd) {
     if (kind == PACOH_KERNEL_RBF) { kv = kd = rbf_exp<T>(T(-0.5) * s2); return; }
     const T s = t_sqrt<T>(s2);
-    T sn, cs;
-    sincospi_t<T>(s, &sn, &cs);
-    kv = cs;
-    kd = s > T(1e-12) ? T(3.141592653589793) * sn / s : T(9.869604401089358);
+    if (kind == PACOH_KERNEL_COSINE) {
+        T sn, cs;
+        sincospi_t<T>(s, &sn, &cs);
+        kv = cs;
+        kd = s > T(1e-12) ? T(3.141592653589793) * sn / s : T(9.869604401089358);
+        return;
+    }
+    if (kind == PACOH_KERNEL_MATERN12) {
+        const T e = rbf_exp<T>(-s);
+        kv = e;
+        kd = s2 > T(1e-30) ? e / s : T(0);
+        return;
+    }
+    const T a = (kind == PACOH_KERNEL_MATERN32 ? T(1.7320508075688772) : T(2.23606797749979)) * s;
+    const T e = rbf_exp<T>(-a);
+    if (kind == PACOH_KERNEL_MATERN32) {
+        kv = (T(1) + a) * e;
+        kd = T(3) * e;
+    } else {
+        kd = (T(1) + a) * e;
+        kv = fma(a * a, T(1.0 / 3.0) * e, kd);
+        kd *= T(5.0 / 3.0);
+    }
 }
 template <typename T> __device__ __forceinline__ T kern_val(int kind, T s2) { T kv, kd; kern_eval<T>(kind, s2, kv, kd); return kv; }
 

@@ -1597,7 +1597,7 @@ extern "C" int pacoh_gp_lml_dense(const void* z, int z_div, const void* mean, in
         return PACOH_EINVAL;
     if (mean_mode != PACOH_MEAN_ZERO && !mean) return PACOH_EINVAL;
     if (d_lengthscale && !d_noise) return PACOH_EINVAL;
-    if (features_of(f) > PACOH_MAX_FEATURES || features_of(f) <= 0 || kernel_of(f) > PACOH_KERNEL_COSINE) return PACOH_ELIMIT;
+    if (features_of(f) > PACOH_MAX_FEATURES || features_of(f) <= 0 || !family_known(kernel_of(f))) return PACOH_ELIMIT;
     if (dtype == PACOH_F32)
         return lml_dense_slabs<float>(z, z_div, mean, mean_mode, y, y_div, lengthscale, outputscale, noise, n_valid, g_lml, lml, d_z, d_mean,
                                       d_lengthscale, d_outputscale, d_noise, info, workspace, workspace_bytes, B, P, n, f, dtype, (hipStream_t)stream);
@@ -1654,7 +1654,7 @@ extern "C" int pacoh_gp_predict_dense(const void* z_ctx, int z_div, const void* 
         m <= 0 || f <= 0 || z_div <= 0 || y_div <= 0 || zt_div <= 0)
         return PACOH_EINVAL;
     if (mean_mode != PACOH_MEAN_ZERO && (!mean_ctx || !mean_tst)) return PACOH_EINVAL;
-    if (features_of(f) > PACOH_MAX_FEATURES || features_of(f) <= 0 || kernel_of(f) > PACOH_KERNEL_COSINE) return PACOH_ELIMIT;
+    if (features_of(f) > PACOH_MAX_FEATURES || features_of(f) <= 0 || !family_known(kernel_of(f))) return PACOH_ELIMIT;
     if (dtype == PACOH_F32)
         return predict_dense_padded<float>(z_ctx, z_div, mean_ctx, mean_mode, y, y_div, z_tst, zt_div, mean_tst, lengthscale, outputscale,
                                            noise, n_valid, mu, var, cov, info, workspace, B, P, n, m, f, dtype, (hipStream_t)stream);

@@ -243,6 +243,59 @@ __device__ __forceinline__ float rcp_(float x) { const float r = __builtin_amdgc
 
 __host__ __device__ constexpr int uidx(int NB, int K, int J) { return K * NB - K * (K - 1) / 2 + (J - K); }   // upper block (K <= J)
 
+// Kernel families of the body (FAM = PACOH_KERNEL_*; common.h: kern_eval).  The features are kept as z * SC / lengthscale, so that a
+// kernel entry is a function of q = |dz|^2 with one v_exp_f32 in it:
+//   RBF        SC^2 = log2(e) / 2:         k / os = exp2(-q)                                    kd = kv
+//   MATERN12   SC = log2(e),          t = sqrt(q) = SC s:  k / os = exp2(-t)                        kd = SC exp2(-t) / t
+//   MATERN32   SC = sqrt(3) log2(e),  x = ln2 t = sqrt(3) s:  k / os = (1 + x) exp2(-t)             kd = 3 exp2(-t)
+//   MATERN52   SC = sqrt(5) log2(e),  x = ln2 t = sqrt(5) s:  k / os = (1 + x + x^2 / 3) exp2(-t)   kd = 5/3 (1 + x) exp2(-t)
+// reg_kvd returns kd without its constant (SC, 3, 5/3), which comes back with 1 / SC^2 in the chain-rule factor DZ: d_z = 2 DZ ... and
+// d_ls = DZ / SC ... (the end of gp_reg_body).  Matern entries take one v_sqrt_f32 (the nu = 1/2 gradient: one v_rsq_f32, giving t and
+// 1 / t) on top of the direct-difference distance -- the |a|^2 + |b|^2 - 2ab form would put fp32 cancellation under the root.  The
+// padding points (far apart, t >= 1e10) still give exact zeros: exp2(-t) = 0 and the polynomial and 1 / t stay finite.
+template <int FAM> struct RegFam;
+template <> struct RegFam<PACOH_KERNEL_RBF> { static constexpr float SC = 0.8493218002880191f, DZ = 1.3862943611198906f; };
+template <> struct RegFam<PACOH_KERNEL_MATERN12> { static constexpr float SC = 1.4426950408889634f, DZ = 0.6931471805599453f; };
+template <> struct RegFam<PACOH_KERNEL_MATERN32> { static constexpr float SC = 2.4988211106473432f, DZ = 0.4804530139182015f; };
+template <> struct RegFam<PACOH_KERNEL_MATERN52> { static constexpr float SC = 3.225964182229561f, DZ = 0.16015100463940043f; };
+constexpr float GPR_LN2 = 0.6931471805599453f, GPR_LN2SQ_3 = 0.16015100463940043f;     // ln 2, (ln 2)^2 / 3
+
+// k / os of one entry (Gram build, predictive K_xs)
+template <int FAM> __device__ __forceinline__ float reg_kv(float q) {
+    if constexpr (FAM == PACOH_KERNEL_RBF) {
+        return __builtin_amdgcn_exp2f(-q);
+    } else {
+        const float t = __builtin_amdgcn_sqrtf(q);
+        const float e = __builtin_amdgcn_exp2f(-t);
+        if constexpr (FAM == PACOH_KERNEL_MATERN12) return e;
+        else if constexpr (FAM == PACOH_KERNEL_MATERN32) return fmaf(GPR_LN2, t, 1.0f) * e;
+        else return fmaf(GPR_LN2, t, fmaf(GPR_LN2SQ_3, q, 1.0f)) * e;
+    }
+}
+// k / os and kd / (its constant) of one entry (gradient loop)
+template <int FAM> __device__ __forceinline__ void reg_kvd(float q, float& kv, float& kd) {
+    if constexpr (FAM == PACOH_KERNEL_RBF) {
+        kv = kd = __builtin_amdgcn_exp2f(-q);
+    } else if constexpr (FAM == PACOH_KERNEL_MATERN12) {
+        // t = q / sqrt(max(q, 1e-30)): sqrt(q), and exactly 0 for coincident points, whose 1 / t = 1e15 then meets a difference of 0
+        // (no gradient, gpytorch's clamped distance) -- one rsq instead of a sqrt and a reciprocal
+        const float rq = __builtin_amdgcn_rsqf(fmaxf(q, 1e-30f));
+        const float e = __builtin_amdgcn_exp2f(-(q * rq));
+        kv = e;
+        kd = e * rq;
+    } else {
+        const float t = __builtin_amdgcn_sqrtf(q);
+        const float e = __builtin_amdgcn_exp2f(-t);
+        if constexpr (FAM == PACOH_KERNEL_MATERN32) {
+            kd = e;
+            kv = fmaf(GPR_LN2, t, 1.0f) * e;
+        } else {
+            kd = fmaf(GPR_LN2, t, 1.0f) * e;
+            kv = fmaf(GPR_LN2SQ_3 * q, e, kd);
+        }
+    }
+}
+
 
 // HAS_OS = false: the caller has no outputscale (SVGD / VI: SEKernelLight, models.py:418-446) -- os == 1 at compile time: the 40
 // multiplies of the Gram build and the 64 additions of the gradient loop that only feed d lml / d outputscale are not compiled in
@@ -259,7 +312,8 @@ __host__ __device__ constexpr int uidx(int NB, int K, int J) { return K * NB - K
 // context rows x test columns), V = L^-1 K_xs as block products with the blocks of L^-1 the backward instantiation keeps in registers,
 // the contractions with K_xs / V on the vector units.  The LDS-resident general kernel it replaces for these shapes ran 20 480
 // problems of n = m = 64 in 1.85 ms; the LML + gradient kernel takes 0.14 for the same batch.
-template <int NB, int FP, bool BWD, bool HAS_OS, class Ctx, bool PRED = false>
+// FAM: the kernel family (RegFam above); gp_reg_matern.hip instantiates the Matern families, every other caller ARD-RBF.
+template <int NB, int FP, bool BWD, bool HAS_OS, class Ctx, bool PRED = false, int FAM = PACOH_KERNEL_RBF>
 __device__ __forceinline__ void gp_reg_body(const GpMfmaArgs& a, const Ctx& cx, float* zf, float* rv,
                                             float* av, float* fsc, float* tsc,
                                             float* dzc, float* Wl, const GpPredArgs* pa = nullptr) {
@@ -282,13 +336,13 @@ __device__ __forceinline__ void gp_reg_body(const GpMfmaArgs& a, const Ctx& cx, 
     int nv = a.n_valid ? a.n_valid[ty] : n;
     nv = nv < n ? nv : n; nv = nv < 0 ? 0 : nv;
 
-    // The features are kept as z * KAPPA / lengthscale, KAPPA^2 = log2(e) / 2: a kernel entry is then exp2(-|dz|^2), ONE
+    // The features are kept as z * SC / lengthscale (RBF: SC^2 = log2(e) / 2): an RBF kernel entry is then exp2(-|dz|^2), ONE
     // instruction on top of the squared distance (104 entries per lane pass through it: 40 of the upper block triangle in the
-    // Gram build, 64 in the gradient loop), and the constant comes back out in the chain-rule factors at the very end.
-    constexpr float KAPPA = 0.8493218002880191f, INV_KAPPA2 = 1.3862943611198906f;
-    float kls[FP];                                            // KAPPA / lengthscale
+    // Gram build, 64 in the gradient loop), and the constant comes back out in the chain-rule factors at the very end (RegFam).
+    constexpr float SC = RegFam<FAM>::SC, DZ = RegFam<FAM>::DZ;
+    float kls[FP];                                            // SC / lengthscale
 #pragma unroll
-    for (int c = 0; c < FP; ++c) kls[c] = (c < f) ? KAPPA * rcp_(a.ls[(long)p * f + c]) : 1.0f;
+    for (int c = 0; c < FP; ++c) kls[c] = (c < f) ? SC * rcp_(a.ls[(long)p * f + c]) : 1.0f;
     const float os = HAS_OS ? (a.os ? a.os[p] : 1.0f) : 1.0f;
     const float noise = a.noise[p];
 
@@ -356,7 +410,7 @@ __device__ __forceinline__ void gp_reg_body(const GpMfmaArgs& a, const Ctx& cx, 
                     float q = 0.0f;
 #pragma unroll
                     for (int c = 0; c < FP; ++c) { const float d = zr[s][c] - zc[c]; q = fmaf(d, d, q); }
-                    const float k = os * __builtin_amdgcn_exp2f(-q);
+                    const float k = os * reg_kv<FAM>(q);
                     blk[s] = (I == J) ? fmaf(nId[s], dadd, -k) : -k;     // (the NEGATED matrix is stored: see the trailing update)
                 }
                 U[uidx(NB, I, J)] = blk;
@@ -493,7 +547,7 @@ __device__ __forceinline__ void gp_reg_body(const GpMfmaArgs& a, const Ctx& cx, 
                     float q = 0.0f;
 #pragma unroll
                     for (int c = 0; c < FP; ++c) { const float d = zf[(16 * I + 4 * g + s) * FP + c] - zt[c]; q = fmaf(d, d, q); }
-                    const float k = os * __builtin_amdgcn_exp2f(-q);
+                    const float k = os * reg_kv<FAM>(q);
                     Ks[I][s] = k;
                     mu_p = fmaf(k, ai4[s], mu_p);
                 }
@@ -561,10 +615,20 @@ __device__ __forceinline__ void gp_reg_body(const GpMfmaArgs& a, const Ctx& cx, 
             float q = 0.0f, df[FP];
 #pragma unroll
             for (int c = 0; c < FP; ++c) { df[c] = zi[c] - zc[c]; q = fmaf(df[c], df[c], q); }
-            const float M = Gij * __builtin_amdgcn_exp2f(-q);
-            if (HAS_OS) msum += live ? M : 0.0f;
+            float kv, kd;
+            reg_kvd<FAM>(q, kv, kd);
+            const float M = Gij * kd;                           // (RBF: kv = kd, one product feeds both sums)
+            if constexpr (FAM == PACOH_KERNEL_RBF) { if (HAS_OS) msum += live ? M : 0.0f; }
+            else { if (HAS_OS) msum += live ? Gij * kv : 0.0f; }
 #pragma unroll
             for (int c = 0; c < FP; ++c) colacc[c] = fmaf(M, df[c], colacc[c]);
+            if constexpr (FAM != PACOH_KERNEL_RBF) {
+                // (Matern: the d_os sum takes its own product G kv, which the scheduler otherwise sinks to the end of the loop, keeping
+                //  every entry's kv alive -- 230 registers of scratch in the 6-block kernel; the sums pass through here entry by entry)
+#pragma unroll
+                for (int c = 0; c < FP; ++c) asm volatile("" : "+v"(colacc[c]));
+                asm volatile("" : "+v"(msum));
+            }
         }
     };
     // ---- W = K^-1, upper block triangle: W[I][J] = sum_{m >= J} Linv[m][I]^T Linv[m][J] ------------------------------------------------
@@ -704,7 +768,7 @@ __device__ __forceinline__ void gp_reg_body(const GpMfmaArgs& a, const Ctx& cx, 
         if (d_z_p && i < n) {
 #pragma unroll
             for (int c = 0; c < FP; ++c)
-                if (c < f) d_z_p[(b * n + i) * (long)f + c] = (i < nv) ? (2.0f * INV_KAPPA2) * osn * gup * dzi[c] * kls[c] + bad : 0.0f;
+                if (c < f) d_z_p[(b * n + i) * (long)f + c] = (i < nv) ? (2.0f * DZ) * osn * gup * dzi[c] * kls[c] + bad : 0.0f;
         }
         if (a.mean_mode == PACOH_MEAN_VECTOR) {
             float* d_mean_p = GPR_LATE(d_mean);
@@ -721,7 +785,7 @@ __device__ __forceinline__ void gp_reg_body(const GpMfmaArgs& a, const Ctx& cx, 
     for (int c = 0; c < FP; ++c) {
         if (c < f) {
             const float sc = -2.0f * osn * wave_sum_(dls[c]);
-            if (lane == 0) GPR_LATE(d_ls)[b * f + c] = (INV_KAPPA2 / KAPPA) * gup * sc * kls[c] + bad;
+            if (lane == 0) GPR_LATE(d_ls)[b * f + c] = (DZ / SC) * gup * sc * kls[c] + bad;
         }
     }
     const float sdos = osn * wave_sum_(msum), sdnz = -osn * wave_sum_(dnz);

@@ -324,7 +324,7 @@ static inline int pow2ceil(int n) { int g = 8; while (g < n) g <<= 1; return g; 
 template <typename T, int MODE>
 static int launch_gp_small(GpArgs<T> a, hipStream_t stream) {
     if (a.B <= 0 || a.P <= 0 || a.n <= 0 || a.f <= 0 || a.z_div <= 0 || a.y_div <= 0) return PACOH_EINVAL;
-    if (a.f > PACOH_MAX_FEATURES || a.kind < 0 || a.kind > PACOH_KERNEL_COSINE) return PACOH_ELIMIT;
+    if (a.f > PACOH_MAX_FEATURES || !family_known(a.kind)) return PACOH_ELIMIT;
     if (!a.z || !a.y || !a.ls || !a.noise) return PACOH_EINVAL;
     if (a.mean_mode != PACOH_MEAN_ZERO && !a.mean) return PACOH_EINVAL;
     const int FP = a.f <= 2 ? 2 : (a.f <= 4 ? 4 : (a.f <= 8 ? 8 : 16));
@@ -398,15 +398,19 @@ struct GpPredArgs {            // (same struct as in gp_reg_body.h)
     float* V_out;
 };
 int gp_reg_predict_try(const GpMfmaArgs& a, const GpPredArgs& pa, hipStream_t s);      // ... its predictive form (n <= 64, no covariance)
+int gp_reg_matern_try(const GpMfmaArgs& a, int kind, bool bwd, hipStream_t s);                        // the same for the Matern
+int gp_reg_matern_predict_try(const GpMfmaArgs& a, const GpPredArgs& pa, int kind, hipStream_t s);    // families (gp_reg_matern.hip)
 }
 static int try_mfma(const GpArgs<float>& a, bool bwd, hipStream_t s) {
-    if (a.kind != PACOH_KERNEL_RBF) return 1;                  // (the register- / LDS-resident MFMA kernels evaluate the RBF family only)
+    // (the register-resident kernels evaluate the RBF and Matern families, the LDS-resident MFMA kernels RBF only; cosine: general kernel)
+    if (a.kind != PACOH_KERNEL_RBF && !family_matern(a.kind)) return 1;
     if (a.n > 128 || a.B <= 0 || a.P <= 0 || a.f <= 0 || a.f > PACOH_MAX_FEATURES ||
         a.z_div <= 0 || a.y_div <= 0 || !a.z || !a.y || !a.ls || !a.noise || (a.mean_mode != PACOH_MEAN_ZERO && !a.mean))
         return 1;
     GpMfmaArgs m = {a.z, a.z_div, a.mean, a.mean_mode, a.y, a.y_div, a.ls, a.os, a.noise, a.n_valid, a.g_lml,
                     a.lml, a.info, a.d_z, a.d_mean, a.d_ls, a.d_os, a.d_noise, a.B, a.P, a.n, a.f};
     // the forward-only entry points may ask for alpha / L outputs, which only the LDS-resident kernels produce: they do not come here
+    if (family_matern(a.kind)) return gp_reg_matern_try(m, a.kind, bwd, s);     // (1 for 4 < f: the general kernel)
     const int rc = gp_reg_try(m, bwd, s);
     if (rc != 1) return rc;
     return gp_mfma_try(m, bwd, s);
@@ -486,14 +490,15 @@ extern "C" int pacoh_gp_predict(const void* z_ctx, int z_div, const void* mean_c
         auto a = make_args<float>(z_ctx, z_div, mean_ctx, mean_mode, y, y_div, lengthscale, outputscale, noise, n_valid, B, P, n, f);
         a.z_tst = (const float*)z_tst; a.zt_div = zt_div; a.mean_tst = (const float*)mean_tst;
         a.mu = (float*)mu; a.var = (float*)var; a.V_out = cov ? (float*)workspace : nullptr; a.m = m; a.info = info;
-        // marginal predictive of an RBF-family GP at n <= 128, f <= 4: the register-resident MFMA kernel (round 5)
+        // marginal predictive of an RBF- or Matern-family GP at n <= 128, f <= 4: the register-resident MFMA kernel (round 5)
         rc = 1;
-        if (a.kind == PACOH_KERNEL_RBF && a.n <= 128 && a.f <= 4 && info && B > 0 && P > 0 && z_div > 0 && y_div > 0 && z_ctx && y &&
+        if ((a.kind == PACOH_KERNEL_RBF || family_matern(a.kind)) && a.n <= 128 && a.f <= 4 && info && B > 0 && P > 0 && z_div > 0 && y_div > 0 && z_ctx && y &&
             lengthscale && noise && (mean_mode == PACOH_MEAN_ZERO || mean_ctx)) {
             GpMfmaArgs ma = {a.z, a.z_div, a.mean, a.mean_mode, a.y, a.y_div, a.ls, a.os, a.noise, a.n_valid, nullptr,
                              nullptr, info, nullptr, nullptr, nullptr, nullptr, nullptr, a.B, a.P, a.n, a.f};
             GpPredArgs pa = {(const float*)z_tst, zt_div, (const float*)mean_tst, (float*)mu, (float*)var, m, a.V_out};
-            rc = gp_reg_predict_try(ma, pa, (hipStream_t)stream);         // (1: not its shape)
+            rc = family_matern(a.kind) ? gp_reg_matern_predict_try(ma, pa, a.kind, (hipStream_t)stream)
+                                       : gp_reg_predict_try(ma, pa, (hipStream_t)stream);         // (1: not its shape)
             if (rc != 0 && rc != 1) return rc;
         }
         if (rc == 1) rc = launch_gp_small<float, MODE_PREDICT>(a, (hipStream_t)stream);

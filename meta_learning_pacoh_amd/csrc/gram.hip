@@ -281,7 +281,7 @@ extern "C" int pacoh_gram_rbf_ard(const void* z1, int z1_div, const void* z2, in
     if (!z1 || !z2 || !lengthscale || !K || B <= 0 || P <= 0 || n <= 0 || m <= 0 || f <= 0 || z1_div <= 0 || z2_div <= 0)
         return PACOH_EINVAL;
     if (add_noise_diag && !noise) return PACOH_EINVAL;
-    if (f > PACOH_MAX_FEATURES || kind < 0 || kind > PACOH_KERNEL_COSINE) return PACOH_ELIMIT;
+    if (f > PACOH_MAX_FEATURES || !family_known(kind)) return PACOH_ELIMIT;
     if (kind != PACOH_KERNEL_RBF) {
         const long total = (long)B * n * m;
         if (dtype == PACOH_F32)

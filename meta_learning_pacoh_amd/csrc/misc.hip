@@ -711,7 +711,7 @@ static int step_begin_launch(const int64_t* idx_all, int tb, const void* sc_all,
                           (T*)aux_out, (const T*)x, (const T*)y, n_valid, (T*)out_x, (T*)out_y, out_n_valid, n * d, n, (const T*)theta,
                           theta_stride, P, off_ls, features_of(f), off_os, off_noise, (T)noise_floor, (T*)ls, (T*)os, (T*)noise,
                           (int)ab, (const T*)svgd_X, d2, svgd_X ? d2 + svgd_P * svgd_P : nullptr, svgd_P, svgd_D,
-                          kernel_of(f) != PACOH_KERNEL_RBF, (const T*)vi_post, (T*)vi_theta, (T*)vi_logq, vi_S, vi_D};
+                          ties_scale(f), (const T*)vi_post, (T*)vi_theta, (T*)vi_logq, vi_S, vi_D};
     const long sb = svgd_X ? (long)svgd_P * svgd_P : 0;
     const dim3 grid((unsigned)(tb + 2 + ab + sb + (vi_post ? vi_S : 0)));
     if (vi_post && vi_sample_nt(vi_D) == 1024) hipLaunchKernelGGL((step_begin_kernel<T, 1024>), grid, dim3(1024), 0, s, a);
@@ -794,7 +794,7 @@ extern "C" void pacoh_reload_env(void) { read_switches(g_sw); }
 extern "C" int pacoh_hyper_fwd(const void* theta, long theta_stride, int P, int off_ls, int f, int off_os, int off_noise,
                                double noise_floor, void* ls, void* os, void* noise, int dtype, void* stream) {
     if (check_dtype(dtype)) return PACOH_EDTYPE;
-    const int tie = kernel_of(f) != PACOH_KERNEL_RBF;
+    const int tie = ties_scale(f);
     f = features_of(f);
     if (!theta || !ls || !noise || P <= 0 || f <= 0 || off_ls < 0 || off_noise < 0) return PACOH_EINVAL;
     unsigned blocks = (unsigned)((P * (f + 2) + 255) / 256);
@@ -818,7 +818,7 @@ extern "C" int pacoh_hyper_bwd(const void* theta, long theta_stride, int P, int 
     if (opt && (!opt->param || !opt->exp_avg || !opt->exp_avg_sq || !opt->scalars || opt->n_seg < 1 || opt->n_seg > 4 || P != 1 || !lml))
         return PACOH_EINVAL;
     if (opt && opt->next) return PACOH_ELIMIT;         // (the pipelined feed's counter is advanced by the fused MLP backward launch)
-    const int tie = kernel_of(f) != PACOH_KERNEL_RBF;
+    const int tie = ties_scale(f);
     f = features_of(f);
     if (!theta || !grad || !d_ls || !d_noise || P <= 0 || T_ <= 0 || f <= 0) return PACOH_EINVAL;
     if ((lml == nullptr) != (lik == nullptr)) return PACOH_EINVAL;
@@ -1005,20 +1005,20 @@ extern "C" int pacoh_svgd_update_next(void* X, const void* score, const void* pr
     if (tb < 0 || (tb > 0 && (!idx_all || !x || !y || !out_x || !out_y || n <= 0 || d <= 0 || (n_valid == nullptr) != (out_n_valid == nullptr))))
         return PACOH_EINVAL;
     const int fdim = features_of(f);
-    if (ls && (!noise || fdim <= 0 || off_ls < 0 || off_noise < 0 || off_noise >= D || off_ls + (kernel_of(f) != PACOH_KERNEL_RBF ? 1 : fdim) > D ||
+    if (ls && (!noise || fdim <= 0 || off_ls < 0 || off_noise < 0 || off_noise >= D || off_ls + (ties_scale(f) ? 1 : fdim) > D ||
                off_os >= D)) return PACOH_EINVAL;
     if (P > PACOH_SVGD_MAX_PARTICLES) return PACOH_ELIMIT;
     if (dtype == PACOH_F32) {
         StepNextArgs<float> nx = {(const long*)counter, (float*)sc2, n_sc, (const long*)idx_all, tb, (const float*)sc_all, (const float*)x,
                                   (const float*)y, n_valid, (float*)out_x, (float*)out_y, out_n_valid, n * d, n, off_ls, fdim, off_os, off_noise,
-                                  kernel_of(f) != PACOH_KERNEL_RBF, (float)noise_floor, (float*)ls, (float*)os, (float*)noise,
+                                  ties_scale(f), (float)noise_floor, (float*)ls, (float*)os, (float*)noise,
                                   bandwidth_ready ? (const float*)workspace + svgd_bw_slot(P, D) : nullptr};
         return svgd_update_next_launch<float>(X, score, prior_mean, prior_std, prior_factor, bandwidth, use_adam, beta1, beta2, exp_avg,
                                               exp_avg_sq, bw_out, workspace, P, D, nx, (hipStream_t)stream);
     }
     StepNextArgs<double> nx = {(const long*)counter, (double*)sc2, n_sc, (const long*)idx_all, tb, (const double*)sc_all, (const double*)x,
                                (const double*)y, n_valid, (double*)out_x, (double*)out_y, out_n_valid, n * d, n, off_ls, fdim, off_os, off_noise,
-                               kernel_of(f) != PACOH_KERNEL_RBF, noise_floor, (double*)ls, (double*)os, (double*)noise,
+                               ties_scale(f), noise_floor, (double*)ls, (double*)os, (double*)noise,
                                bandwidth_ready ? (const double*)workspace + svgd_bw_slot(P, D) : nullptr};
     return svgd_update_next_launch<double>(X, score, prior_mean, prior_std, prior_factor, bandwidth, use_adam, beta1, beta2, exp_avg,
                                            exp_avg_sq, bw_out, workspace, P, D, nx, (hipStream_t)stream);

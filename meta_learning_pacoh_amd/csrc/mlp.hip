@@ -278,7 +278,7 @@ static bool step_next_ok(const pacoh_step_next* x) {
 static StepNextArgs<float> step_next_f32(const pacoh_step_next* x, int off_ls, int f, int off_os, int off_noise) {
     return StepNextArgs<float>{(const long*)x->counter, (float*)x->sc2, x->n_sc, (const long*)x->idx_all, x->tb, (const float*)x->sc_all,
                                (const float*)x->x, (const float*)x->y, x->n_valid, (float*)x->out_x, (float*)x->out_y, x->out_n_valid,
-                               x->n * x->d, x->n, off_ls, features_of(f), off_os, off_noise, kernel_of(f) != PACOH_KERNEL_RBF,
+                               x->n * x->d, x->n, off_ls, features_of(f), off_os, off_noise, ties_scale(f),
                                (float)x->noise_floor, (float*)x->ls, (float*)x->os, (float*)x->noise, nullptr};
 }
 // the same step as separate launches (paths without the fused slab reduction): one pacoh_adam_step_dev per trained segment, the last
@@ -369,7 +369,7 @@ extern "C" int pacoh_mlp2_bwd_hyper(const void* x, int x_div, const void* theta,
         HyperBwdArgs<float> tail = {(const float*)theta, theta_stride, P, T_, off_ls, features_of(f), off_os, off_noise, off_const,
                                     (const float*)d_ls, (const float*)d_os, (const float*)d_noise, (const float*)d_const, (float*)d_theta,
                                     d_theta_stride, (const float*)lml, (float*)lik, (float)lik_scale, info, fail_flag,
-                                    kernel_of(f) != PACOH_KERNEL_RBF, (const float*)svgd_workspace, svgd_P,
+                                    ties_scale(f), (const float*)svgd_workspace, svgd_P,
                                     svgd_workspace ? (float*)svgd_workspace + svgd_bw_slot(svgd_P, svgd_D) : nullptr,
                                     opt ? adam_inline_f32(opt) : AdamInline<float>{},
                                     (opt && opt->next) ? step_next_f32(opt->next, off_ls, f, off_os, off_noise) : StepNextArgs<float>{}};
@@ -414,7 +414,7 @@ extern "C" int pacoh_mlp_bwd_hyper(const void* x, int x_div, const void* theta, 
         HyperBwdArgs<float> tail = {(const float*)theta_rows, theta_stride, P, T_, off_ls, features_of(f), off_os, off_noise, off_const,
                                     (const float*)d_ls, (const float*)d_os, (const float*)d_noise, (const float*)d_const, (float*)grad_rows,
                                     d_theta_stride, (const float*)lml, (float*)lik, (float)lik_scale, info, fail_flag,
-                                    kernel_of(f) != PACOH_KERNEL_RBF, (const float*)svgd_workspace, svgd_P,
+                                    ties_scale(f), (const float*)svgd_workspace, svgd_P,
                                     svgd_workspace ? (float*)svgd_workspace + svgd_bw_slot(svgd_P, svgd_D) : nullptr,
                                     opt ? adam_inline_f32(opt) : AdamInline<float>{},
                                     (opt && opt->next) ? step_next_f32(opt->next, off_ls, f, off_os, off_noise) : StepNextArgs<float>{}};

@@ -31,6 +31,10 @@ def nn_param_layout(input_dim, output_dim, layer_sizes):
     return layout
 
 
+# covar_module kind of a ParamLayout -> its PACOH_KERNEL_* family ('NN': ARD-RBF on the learned features)
+KERNEL_CODES = {'SE': L.KERNEL_RBF, 'COS': L.KERNEL_COSINE, 'M12': L.KERNEL_MATERN12, 'M32': L.KERNEL_MATERN32, 'M52': L.KERNEL_MATERN52}
+
+
 class ParamLayout:
     """Flattened prior-parameter vector.  Block order follows VectorizedGP.__init__
     (meta_learn/random_gp.py:33-51): mean block, kernel_nn block, lengthscale_raw, [outputscale_raw,]
@@ -40,9 +44,11 @@ class ParamLayout:
                  kernel_nn_layers=(32, 32), feature_dim=2, with_outputscale=False):
         # 'COS': gpytorch.kernels.CosineKernel on the raw inputs (module objects only, modules.py) -- ONE raw period parameter, kept
         # in the lengthscale slot; the device sees it replicated over the input dimensions (PACOH_KERNEL_COSINE in pacoh_gp.h)
-        assert mean_module in ('NN', 'constant', 'zero') and covar_module in ('NN', 'SE', 'COS')
+        # 'M12' | 'M32' | 'M52': gpytorch.kernels.MaternKernel(nu = 1/2, 3/2, 5/2) on the raw inputs (module objects only) -- ARD
+        # lengthscales like 'SE', one raw parameter per input dimension (PACOH_KERNEL_MATERN*)
+        assert mean_module in ('NN', 'constant', 'zero') and covar_module in ('NN',) + tuple(KERNEL_CODES)
         self.input_dim, self.mean_module, self.covar_module = input_dim, mean_module, covar_module
-        self.kernel_code = L.KERNEL_COSINE if covar_module == 'COS' else L.KERNEL_RBF
+        self.kernel_code = KERNEL_CODES.get(covar_module, L.KERNEL_RBF)
         self.mean_nn_layers, self.kernel_nn_layers = tuple(mean_nn_layers), tuple(kernel_nn_layers)
         self.feature_dim = feature_dim if covar_module == 'NN' else input_dim
         self.with_outputscale = with_outputscale

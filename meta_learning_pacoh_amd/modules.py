@@ -1,9 +1,10 @@
 """`mean_module` / `covar_module` arguments given as OBJECTS.  The reference accepts gpytorch.means.Mean / gpytorch.kernels.Kernel
 instances besides the strings (meta_learn/GPR_meta_mll.py:207-251, GPR_mll.py:45-90) and hands them to ExactGP as they are.  The
-HIP path implements two kernel families -- ARD-RBF on raw inputs or on learned features, and (round 3) the cosine kernel on raw
-inputs, both optionally scaled -- and zero / constant / network means, so an object is accepted exactly when it denotes one of
-those: ZeroMean, ConstantMean, RBFKernel, CosineKernel (the reference's own tests/test_GPR.py:95-101 hands one to the single-task
-learner) and ScaleKernel(...) of either, recognised by class name anywhere in the object's MRO (gpytorch itself is not needed, and
+HIP path implements these kernel families -- ARD-RBF on raw inputs or on learned features, (round 3) the cosine kernel and the
+ARD Matern kernels with nu = 1/2, 3/2, 5/2 on raw inputs, all optionally scaled -- and zero / constant / network means, so an object
+is accepted exactly when it denotes one of those: ZeroMean, ConstantMean, RBFKernel, CosineKernel (the reference's own
+tests/test_GPR.py:95-101 hands one to the single-task learner), MaternKernel with one of those `nu` and ScaleKernel(...) of any of
+them, recognised by class name anywhere in the object's MRO (gpytorch itself is not needed, and
 not present, on the GPU box).  Their current raw hyper-parameters become the initial values.  Anything else raises
 NotImplementedError: it cannot be evaluated by these kernels."""
 import math
@@ -49,8 +50,11 @@ def resolve_mean_module(mean_module):
                               % type(mean_module).__name__)
 
 
+MATERN_NU = {0.5: 'M12', 1.5: 'M32', 2.5: 'M52'}      # gpytorch.kernels.MaternKernel(nu) -> ParamLayout covar kind
+
+
 def resolve_covar_module(covar_module):
-    """-> ('NN' | 'SE' | 'COS', initial raw values {'lengthscale_raw': [...], 'outputscale_raw': v}, learn_outputscale)"""
+    """-> ('NN' | 'SE' | 'COS' | 'M12' | 'M32' | 'M52', initial raw values {'lengthscale_raw': [...], 'outputscale_raw': v}, learn_outputscale)"""
     if isinstance(covar_module, str):
         return covar_module, {}, True
     names = _names(covar_module)
@@ -62,9 +66,11 @@ def resolve_covar_module(covar_module):
         kind, raw = 'SE', 'raw_lengthscale'
     elif 'CosineKernel' in base_names:                         # k = cos(pi |x - x'| / period_length): ONE raw period parameter
         kind, raw = 'COS', 'raw_period_length'
+    elif 'MaternKernel' in base_names and _scalar(getattr(base, 'nu', None)) in MATERN_NU:
+        kind, raw = MATERN_NU[_scalar(base.nu)], 'raw_lengthscale'
     else:
-        raise NotImplementedError('covar_module object of type %s: the HIP path evaluates the (scaled) ARD-RBF and cosine kernels only'
-                                  % type(covar_module).__name__)
+        raise NotImplementedError('covar_module object of type %s: the HIP path evaluates the (scaled) ARD-RBF, cosine and Matern '
+                                  '(nu = 0.5, 1.5, 2.5) kernels only' % type(covar_module).__name__)
     init = {}
     ls = _vector(getattr(base, raw, None))
     if ls:
