@@ -537,11 +537,31 @@ int pacoh_reduce_tasks(const void* in, void* out, double scale, int accumulate, 
  *                       one launch for the T test tasks of eval_datasets (abstract.py:165-181).
  * pacoh_mixture_icdf takes ONE task (mu, var [P,m]). */
 #define PACOH_MAX_QUANTILES 2048
+
 int pacoh_mixture_cdf(const void* mu, const void* var, const void* value, void* cdf, double y_mean, double y_std, int T, int P,
                       int m, int dtype, void* stream);
 int pacoh_mixture_icdf(const void* mu, const void* var, const void* quantile, void* out, double y_mean, double y_std, double lo,
                        double hi, double eps, int max_iter, int closed_form, int P, int m, int dtype, void* stream);
 int pacoh_calib_error(const void* cdf, void* out, int T, int m, int dtype, void* stream);
+
+/* ---- 8g: joint draws from the posterior predictive ----------------------------------------------------------------------------
+ * The reference's predictive AffineTransformedDistribution(likelihood(gp(x))) (meta_learn/models.py:15-43, returned by
+ * GPR_meta_mll.py:181-186 and GPR_mll.py:194-198) draws with MultivariateNormal.rsample: gpytorch's psd_safe_cholesky of the
+ * covariance, then mean + L eps, then the affine un-normalisation.  Always Cholesky (no Lanczos root above max_cholesky_size).
+ *   pacoh_mvn_factor: L[b] (lower triangle) = chol(cov[b] + j_b I) for B covariances [B,m,m]; cov is read (lower triangle) and NOT
+ *                     modified.  info[b] = the rung used: 0 = no jitter, k = 1..3 -> j = base 10^(k-1), base 1e-6 (fp32) / 1e-8 (fp64),
+ *                     the ladder of the dense GP path; < 0 = not positive definite after rung 3.  The dense Cholesky of
+ *                     pacoh_mvn_logprob_dense factors (by size); its upper triangle holds scratch.  workspace: the
+ *                     pacoh_mvn_factor_workspace_bytes() query.  m <= 65535; sizes the dense Cholesky rejects: PACOH_ELIMIT.
+ *   pacoh_mvn_sample: out[s,:] = y_mean + y_std (mu[c_s,:] + L[c_s] eps[s,:]) for S draws (eps, out [S,m] in DRAW order; mu [B,m]).
+ *                     The draws are grouped by component: order[offsets[c] .. offsets[c+1]) are the draws of component c
+ *                     (int32 device arrays, offsets[0] = 0, offsets[B] = S, every draw once); order = offsets = NULL only when
+ *                     B == 1 (every draw from component 0).  Rows of a component with info[c] < 0 are NaN.  S == 0 launches nothing.
+ *                     One launch for all components; the grid follows the draws each component received. */
+size_t pacoh_mvn_factor_workspace_bytes(int B, int m, int dtype);
+int pacoh_mvn_factor(const void* cov, void* L, int32_t* info, void* workspace, int B, int m, int dtype, void* stream);
+int pacoh_mvn_sample(const void* L, const int32_t* info, const void* mu, const void* eps, const int32_t* order,
+                     const int32_t* offsets, void* out, double y_mean, double y_std, int B, int m, int S, int dtype, void* stream);
 
 /* ---- K whole PACOH-MAP iterations per launch (round 5) ------------------------------------------
  * The reference's own regime -- a handful of small tasks per iteration (demo.py:14-26: 5 tasks x 5 points) -- is pure launch

@@ -103,6 +103,9 @@ SIGNATURES = {
     'pacoh_mixture_cdf': (_i, [_vp, _vp, _vp, _vp, _d, _d, _i, _i, _i, _i, _vp]),
     'pacoh_mixture_icdf': (_i, [_vp, _vp, _vp, _vp, _d, _d, _d, _d, _d, _i, _i, _i, _i, _i, _vp]),
     'pacoh_calib_error': (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    'pacoh_mvn_factor_workspace_bytes': (_sz, [_i, _i, _i]),
+    'pacoh_mvn_factor': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'pacoh_mvn_sample': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _i, _i, _i, _i, _vp]),
     'pacoh_map_persist_supported': (_i, [_i, _i, _i, _i, _ip, _i, _i, _ip, _i, _i, _i]),
     'pacoh_map_persist': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _ip, _i, _i, _i, _ip, _i, _i,
                                _i, _i, _i, _d, _ip, _ip, _i, _d, _d, _vp, _vp, _vp, _i, _vp]),
@@ -1233,6 +1236,49 @@ def mixture_icdf(mu_n, var_n, quantile, y_mean, y_std, closed_form=False, lo=-1e
         _check(lib.pacoh_mixture_icdf(_ptr(mu_n), _ptr(var_n, mu_n), _ptr(quantile, mu_n), _ptr(out), float(y_mean), float(y_std),
                                       float(lo), float(hi), float(eps), int(max_iter), int(bool(closed_form)), P, m,
                                       dtype_code(mu_n), _stream()), 'pacoh_mixture_icdf')
+    return out
+
+
+def mvn_factor(cov):
+    """L [B,m,m] (lower triangle; the upper holds scratch) = chol(cov + j I) with the jitter ladder, info [B] int32 = the rung used
+    (< 0: failed).  cov [B,m,m] is left intact."""
+    lib = load_library()
+    if cov.dim() != 3 or cov.shape[1] != cov.shape[2]:
+        raise ValueError('cov must be [B,m,m], got %s' % (tuple(cov.shape),))
+    cov = cov.contiguous()
+    B, m = cov.shape[0], cov.shape[-1]
+    Lf = torch.empty_like(cov)
+    info = torch.empty(B, dtype=torch.int32, device=cov.device)
+    ws = _workspace('mvn_factor', lib.pacoh_mvn_factor_workspace_bytes(B, m, dtype_code(cov)), cov.device)
+    with _Timed('mvn_factor'):
+        _check(lib.pacoh_mvn_factor(_ptr(cov), _ptr(Lf, cov), _ptr(info), _ptr(ws), B, m, dtype_code(cov), _stream()), 'pacoh_mvn_factor')
+    return Lf, info
+
+
+def mvn_sample(Lf, info, mu, eps, y_mean=0.0, y_std=1.0, order=None, offsets=None):
+    """out [S,m] = y_mean + y_std (mu[c_s] + L[c_s] eps[s]) in draw order; Lf, info from mvn_factor, mu [B,m], eps [S,m]; the draws of
+    component c are order[offsets[c] : offsets[c+1]] (int32; None, None: B == 1)"""
+    lib = load_library()
+    if mu.dim() != 2:
+        raise ValueError('mu must be [B,m], got %s' % (tuple(mu.shape),))
+    B, m = mu.shape
+    if Lf.dim() != 3 or Lf.shape[0] < B or tuple(Lf.shape[1:]) != (m, m):
+        raise ValueError('Lf must be [>=%d,%d,%d], got %s' % (B, m, m, tuple(Lf.shape)))
+    if info.dtype != torch.int32 or info.numel() < B:
+        raise ValueError('info must be int32 with >= %d entries, got %s %s' % (B, info.dtype, tuple(info.shape)))
+    if eps.dim() != 2 or eps.shape[1] != m:
+        raise ValueError('eps must be [S,%d], got %s' % (m, tuple(eps.shape)))
+    S = eps.shape[0]
+    if (order is None) != (offsets is None) or (order is None and B > 1):
+        raise ValueError('order and offsets come together, and are required when B > 1')
+    if order is not None and (order.dtype != torch.int32 or offsets.dtype != torch.int32 or order.numel() != S
+                              or offsets.numel() != B + 1):
+        raise ValueError('order must be int32 [%d] and offsets int32 [%d], got %s %s / %s %s'
+                         % (S, B + 1, order.dtype, tuple(order.shape), offsets.dtype, tuple(offsets.shape)))
+    out = torch.empty(S, m, dtype=mu.dtype, device=mu.device)
+    with _Timed('mvn_sample'):
+        _check(lib.pacoh_mvn_sample(_ptr(Lf), _ptr(info), _ptr(mu, Lf), _ptr(eps, Lf), _ptr(order), _ptr(offsets), _ptr(out, Lf),
+                                    float(y_mean), float(y_std), B, m, S, dtype_code(Lf), _stream()), 'pacoh_mvn_sample')
     return out
 
 

@@ -238,6 +238,15 @@ int dense_chol_retry_fused(void* A, const void* resid, void* logp, void* alpha_o
                               jitter_base, P, f, kind, stream);
 }
 
+// true when dense_chol_launch() has a kernel for this size (the routing below, without launching): callers that enqueue work of their
+// own in front of the factorisation ask first
+bool dense_chol_fits(int n, int dtype) {
+    if (ll_enabled() && n >= LL_MIN_N && dense_ll_fits(n, dtype)) return true;
+    if (dense_mfma_fits(n, dtype)) return true;
+    const size_t lds = ((size_t)n + NB * (NB + 1) + 2 * TT * (NB + 1) + NB + 8) * (dtype == PACOH_F64 ? 8 : 4);
+    return lds <= 64u * 1024u;
+}
+
 // u_only (only honoured on the MFMA path, i.e. when dense_chol_saves_inverse()): alpha_out receives u = L^-1 r instead of alpha
 int dense_chol_launch(void* A, const void* resid, void* logp, void* alpha_out, int32_t* info, double scale, int B, int n,
                       int dtype, int attempt, hipStream_t stream, int u_only) {

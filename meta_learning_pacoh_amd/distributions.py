@@ -2,13 +2,18 @@
 
 They play the role of AffineTransformedDistribution(MultivariateNormal) (meta_learn/models.py:15-43) and
 EqualWeightedMixtureDist(batched=True) (models.py:74-140) in the reference: .mean, .stddev, .variance,
-.log_prob (JOINT Gaussian log-density over all test points, per component), .cdf / .icdf (marginals).
-The joint log-density runs the dense HIP Cholesky kernel on the predictive covariance."""
+.log_prob (JOINT Gaussian log-density over all test points, per component), .cdf / .icdf (marginals), and joint draws
+.sample / .rsample (MultivariateNormal.rsample of the reference's single-Gaussian predictive).
+The joint log-density runs the dense HIP Cholesky kernel on the predictive covariance; the draws factor it once per object
+(pacoh_mvn_factor) and transform the standard normals on the matrix cores (pacoh_mvn_sample)."""
 import math
 
 import torch
 
 from . import _lib as L
+from .engine import NotPSDError
+
+_NO_COV = 'predict(..., return_density=True) must be called to get the joint covariance'
 
 
 class GaussianPredictive:
@@ -20,6 +25,7 @@ class GaussianPredictive:
         self.y_mean, self.y_std = float(y_mean), float(y_std)
         self.mixture = mixture
         self.num_dists = mu_n.shape[0]
+        self._chol = None                    # (L [P,m,m], info [P]) of the first draw, reused by every later one
 
     # -- component moments in original units ------------------------------------------------------
     @property
@@ -50,7 +56,7 @@ class GaussianPredictive:
     def log_prob(self, value):
         """joint log-density of the m test targets (original units); mixture: logsumexp - log P"""
         if self._cov_n is None:
-            raise RuntimeError('predict(..., return_density=True) must be called to get the joint covariance')
+            raise RuntimeError(_NO_COV)
         value = torch.as_tensor(value, dtype=self._mu_n.dtype, device=self._mu_n.device).flatten()
         m = value.shape[0]
         resid = ((value - self.y_mean) / self.y_std).unsqueeze(0) - self._mu_n              # [P,m]
@@ -71,3 +77,61 @@ class GaussianPredictive:
         quantile = torch.as_tensor(quantile, dtype=self._mu_n.dtype, device=self._mu_n.device)
         return L.mixture_icdf(self._mu_n.contiguous(), self._var_n.contiguous(), quantile, self.y_mean, self.y_std,
                               closed_form=not self.mixture)
+
+    # -- joint draws ------------------------------------------------------------------------------
+    def _factor(self):
+        """the Cholesky factors of the P component covariances with gpytorch's jitter ladder, computed on the first draw (one host
+        sync, to read which components failed) and kept; the covariance itself stays intact"""
+        if self._chol is None:
+            Lf, info = L.mvn_factor(self._cov_n)
+            bad = torch.nonzero(info < 0).flatten().tolist()
+            self._chol = (Lf, info, bad)
+        Lf, info, bad = self._chol
+        if bad:
+            raise NotPSDError('predictive covariance of component %s is not positive definite even after adding jitter (%s)'
+                              % (', '.join(str(c) for c in bad), '1e-6 .. 1e-4' if self._mu_n.dtype == torch.float32 else '1e-8 .. 1e-6'))
+        return Lf, info
+
+    def rsample(self, sample_shape=torch.Size(), base_samples=None):
+        """joint draws of the m test targets in original units, shape [*sample_shape, m]: y_mean + y_std (mu_c + L_c eps), L_c the
+        jittered Cholesky factor of component c's predictive covariance (observation noise included, as likelihood(gp(x))).
+
+        base_samples [*sample_shape, m]: the standard normals eps (then sample_shape is read from them, as gpytorch's
+        MultivariateNormal.rsample does); otherwise eps are drawn on the device.  Draw order on the device generator, fixed:
+        1. mixture only: the component of every draw, torch.randint(P, (S,));  2. eps = torch.randn(S, m).
+        One component (mixture=False): every draw from component 0, as the reference.  Mixture: each draw picks a component uniformly
+        and draws from it -- an extension, the reference's EqualWeightedMixtureDist (models.py:74-140) cannot sample.
+        No autograd graph is built.  Raises engine.NotPSDError when a component is not positive definite after the jitter ladder."""
+        if self._cov_n is None:
+            raise RuntimeError(_NO_COV)
+        mu_n = self._mu_n
+        dev, dt = mu_n.device, mu_n.dtype
+        m, P = mu_n.shape[1], self.num_dists
+        with torch.no_grad():
+            if base_samples is not None:
+                base_samples = torch.as_tensor(base_samples, dtype=dt, device=dev)
+                if base_samples.dim() < 1 or base_samples.shape[-1] != m:
+                    raise RuntimeError('base_samples must have shape [*sample_shape, %d], got %s' % (m, tuple(base_samples.shape)))
+                sample_shape = base_samples.shape[:-1]
+            sample_shape = torch.Size(sample_shape)
+            S = sample_shape.numel()
+            if S == 0:
+                return torch.empty(*sample_shape, m, dtype=dt, device=dev)
+            Lf, info = self._factor()
+            comp = torch.randint(P, (S,), device=dev) if self.mixture else None
+            eps = (base_samples.reshape(S, m).contiguous() if base_samples is not None
+                   else torch.randn(S, m, dtype=dt, device=dev))
+            if comp is not None and P > 1:
+                # (device-side grouping: a stable sort and the component boundaries in it -- no host sync)
+                sorted_comp, order = torch.sort(comp, stable=True)
+                order = order.to(torch.int32)
+                offsets = torch.searchsorted(sorted_comp, torch.arange(P + 1, device=dev)).to(torch.int32)
+                out = L.mvn_sample(Lf, info, mu_n.contiguous(), eps, self.y_mean, self.y_std, order, offsets)
+            else:
+                out = L.mvn_sample(Lf[:1], info[:1], mu_n[:1].contiguous(), eps, self.y_mean, self.y_std)
+        return out.reshape(*sample_shape, m)
+
+    def sample(self, sample_shape=torch.Size()):
+        """the draws of rsample under torch.no_grad()"""
+        with torch.no_grad():
+            return self.rsample(sample_shape)
