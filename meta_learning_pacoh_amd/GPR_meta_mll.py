@@ -2,22 +2,19 @@
 GPRegressionMetaLearned (meta_learn/GPR_meta_mll.py:12-264); the per-task ExactGP + autograd + AdamW
 loop (:104-117) runs as a handful of HIP kernel launches per iteration over the whole task batch."""
 import os
-import time
 from collections import OrderedDict
 
-import numpy as np
 import torch
 
 from . import _lib as L
 from . import parallel
 from .abstract import RegressionModelMetaLearned
-from .distributions import GaussianPredictive
-from .engine import GPEngine, NotPSDError, ParamLayout, StepFeed, StepMode, TaskBatch, build_step_graphs, replay_steps, run_step
+from .engine import GPEngine, ParamLayout, StepDriver, StepMode, TaskBatch
 from .modules import apply_initial_values, resolve_covar_module, resolve_mean_module
 from .util import StepLR
 
 
-class GPRegressionMetaLearned(RegressionModelMetaLearned):
+class GPRegressionMetaLearned(StepDriver, RegressionModelMetaLearned):
 
     def __init__(self, meta_train_data, learning_mode='both', lr_params=1e-3, weight_decay=0.0, feature_dim=2,
                  num_iter_fit=10000, covar_module='NN', mean_module='NN', mean_nn_layers=(32, 32),
@@ -110,7 +107,6 @@ class GPRegressionMetaLearned(RegressionModelMetaLearned):
         self.exp_avg_sq = torch.zeros_like(self.theta)
         self.opt_step = 0
         self.lr_scheduler = StepLR(lr, 1000, lr_decay)
-        self._feed = self._graphs = None
         self._step_mode = StepMode()
 
     # ---- one meta-training iteration captured in hipGraph(s) ---------------------------------------------------------------------
@@ -120,19 +116,14 @@ class GPRegressionMetaLearned(RegressionModelMetaLearned):
     # ranks the task batch is sharded (rank r evaluates idx[r::world]) and grad[1,D] + loss -- sums over tasks
     # (GPR_meta_mll.py:109-113) -- are all-reduced between the two graphs of a step.  Same kernels, same order, same results
     # eagerly (PACOH_NO_GRAPH=1).
-    GRAPH_CHUNK = 1024
+    _STEP_STATE = ('theta', 'exp_avg', 'exp_avg_sq', '_g_cum')
 
-    def _setup_step(self):
-        if getattr(self, '_feed', None) is not None:
+    def _setup_step(self, tb_local):
+        if self._feed is not None and self._feed.tb == tb_local:
             return
-        D = self.layout.D
-        tb_local = len(parallel.shard(np.arange(self.task_batch_size)))
-        self._packed = torch.zeros(D + 1, dtype=self.dtype, device=self.device)      # grad[1, D] | loss: ONE all-reduce operand
-        self._grad, self._g_loss = self._packed[:D].view(1, D), self._packed[D:]
         self._g_cum = torch.zeros((), dtype=self.dtype, device=self.device)
-        self._fail = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self._feed = StepFeed(self.device, self.dtype, tb_local, chunk=self.GRAPH_CHUNK)
-        self._graphs = self._opt_blk = None
+        self._grad, self._g_loss = self._new_step(tb_local, 1, self.GRAPH_CHUNK)      # grad[1, D] | loss: ONE all-reduce operand
+        self._opt_blk = None
         # The reference's own regime -- a handful of small tasks per iteration -- runs K whole iterations per launch in one
         # workgroup (include/pacoh_gp.h, pacoh_map_persist): world size 1, Adam, a shape the kernel takes.  PACOH_MAP_PERSIST=0: the
         # launch sequence below (tests compare the two)
@@ -227,77 +218,28 @@ class GPRegressionMetaLearned(RegressionModelMetaLearned):
             else:
                 L.axpy(self.theta[0, lo:hi], self._grad[0, lo:hi], -self.lr_scheduler.lr)       # (eager only: host scalar)
 
-    def _all_reduce(self):
-        parallel.all_reduce_buffer_(self._packed)         # ONE exchange per iteration: grad [1, D] | loss, in place
+    def _graphs_allowed(self):
+        # (the persistent kernel has nothing to capture: one launch per chunk)
+        return self._persist is None and self.optimizer_name == 'Adam' and super()._graphs_allowed()
 
-    def _build_graphs(self):
-        state = (self.theta, self.exp_avg, self.exp_avg_sq, self._feed.ctr, self._fail, self._g_cum)
-        saved = [t.clone() for t in state]
-        # (the large-context path allocates O(tasks x n^2) scratch per step inside the graph's pool: one step per graph there)
-        self._graphs, self._graph_many = build_step_graphs(self._body_likelihood, self._all_reduce, self._body_update, self._feed,
-                                                           many_ok=self.tasks.n <= 128)
-        for t, sv in zip(state, saved):
-            t.copy_(sv)
-        if self._pipelined:
-            self._feed.prologue()                         # (batch buffers, scalars and hyper-parameters of the restored parameters)
+    def _chunk_size(self, n_steps, last):
+        # (no small first chunk; SGD reads the host-side learning rate: one step per chunk)
+        return min(n_steps, self._feed.chunk) if self.optimizer_name == 'Adam' else 1
 
-    def _run_step(self, graphed):
-        run_step(self._graphs, graphed, self._body_likelihood, self._all_reduce, self._body_update)
+    def _step_scalars(self, idx):
+        return L.step_scalar_rows(1.0, self.lr_scheduler.lrs(len(idx)), self.opt_step + 1, weight_decay=self.weight_decay)
 
-    def _use_graph(self):
-        # (large contexts run the HBM-resident path, whose launch sequence sets kernel attributes: keep it eager)
-        return (self.optimizer_name == 'Adam' and os.environ.get('PACOH_NO_GRAPH', '0') != '1'
-                and self.tasks.n <= L.gp_small_max_n(self.dtype, True) and not L.FORCE_DENSE)
+    def _prologue(self):
+        super()._prologue()
+        if self._task_ws is not None:                    # (theta may have been set from outside since the last call; a capture's runs
+            L.map_task_setup(self._task_plan, self.theta, self._feed.tb, self._task_ws)      # stepped the image along with theta)
 
-    def _train_steps_persist(self, n_steps):
-        """K iterations per launch: the task draws and step scalars of a chunk go up in one copy each (engine.StepFeed), one
-        launch runs the chunk.  Same draws from rds_numpy, same scalars as the launch sequence."""
-        while n_steps > 0:
-            k = min(n_steps, self.GRAPH_CHUNK)
-            idx = self.rds_numpy.randint(0, self.tasks.T, size=(k, self.task_batch_size))
-            sc_rows = L.step_scalar_rows(1.0, self.lr_scheduler.lrs(k), self.opt_step + 1, weight_decay=self.weight_decay)
-            self._feed.upload(idx, sc_rows)
-            L.map_persist(self._persist, self.theta, self.exp_avg, self.exp_avg_sq, self.tasks, self._feed.idx_all, self._feed.sc_all, k,
-                          self._g_loss, self._g_cum.reshape(1), self._fail)
-            self.opt_step += k
-            for _ in range(k):
-                self.lr_scheduler.step()
-            n_steps -= k
-
-    def _train_steps(self, n_steps):
-        self._setup_step()
-        if self._persist is not None:
-            return self._train_steps_persist(n_steps)
-        graphed = self._use_graph()
-        while n_steps > 0:
-            k = min(n_steps, self.GRAPH_CHUNK) if self.optimizer_name == 'Adam' else 1     # SGD reads the host-side learning rate
-            # rds_numpy.choice(task_dicts, size=B) == randint(0, T, B): with replacement (GPR_meta_mll.py:109); one call of shape
-            # [k, B] consumes the numpy stream exactly like k calls
-            idx = self.rds_numpy.randint(0, self.tasks.T, size=(k, self.task_batch_size))
-            sc_rows = L.step_scalar_rows(1.0, self.lr_scheduler.lrs(k), self.opt_step + 1, weight_decay=self.weight_decay)
-            rank, world = parallel.world()
-            local = np.ascontiguousarray(idx[:, rank::world])
-            parallel.check_same_draws(local, sc_rows)
-            self._feed.upload(local if self._feed.tb > 0 else None, sc_rows)
-            if self._pipelined:
-                self._feed.prologue()
-            if self._task_ws is not None:                # (theta may have been set from outside since the last call)
-                L.map_task_setup(self._task_plan, self.theta, self._feed.tb, self._task_ws)
-            if graphed and self._graphs is None:
-                self._build_graphs()
-                if self._task_ws is not None:            # (the capture runs stepped the image along with theta; theta was restored)
-                    L.map_task_setup(self._task_plan, self.theta, self._feed.tb, self._task_ws)
-            if graphed:
-                # replay or eager launches, whichever is faster here (engine.StepMode); several steps per replay where possible
-                many = (lambda n: replay_steps(n, self._graphs[0], self._graph_many)) if len(self._graphs) == 1 else None
-                self._step_mode.run(k, self._run_step, many)
-            else:
-                for _ in range(k):
-                    self._run_step(False)
-            self.opt_step += k
-            for _ in range(k):
-                self.lr_scheduler.step()
-            n_steps -= k
+    def _run_chunk(self, k, graphed):
+        if self._persist is None:
+            return super()._run_chunk(k, graphed)
+        # K iterations per launch: the chunk's task draws and step scalars, uploaded as for the launch sequence, in one launch
+        L.map_persist(self._persist, self.theta, self.exp_avg, self.exp_avg_sq, self.tasks, self._feed.idx_all, self._feed.sc_all, k,
+                      self._g_loss, self._g_cum.reshape(1), self._fail)
 
     # ------------------------------------------------------------------------------------------
     def meta_fit(self, valid_tuples=None, verbose=True, log_period=500, n_iter=None):
@@ -305,30 +247,14 @@ class GPRegressionMetaLearned(RegressionModelMetaLearned):
         assert (valid_tuples is None) or (all([len(valid_tuple) == 4 for valid_tuple in valid_tuples]))
         loss_val = float('nan')
         if len(self.train_segments) > 0:
-            t = time.time()
-            if n_iter is None:
-                n_iter = self.num_iter_fit
-            self._setup_step()
+            self._setup_step(self._local_batch_size())
             self._g_cum.zero_()
-            itr = 0
-            while itr < n_iter:
-                nxt = 1 if itr == 0 else min(n_iter, (itr // log_period + 1) * log_period)      # up to the next log line
-                self._train_steps(nxt - itr)
-                itr = nxt
-                if itr == 1 or itr % log_period == 0:
-                    duration = time.time() - t
-                    avg_loss = self._g_cum / (log_period if itr > 1 else 1.0)
-                    message = 'Iter %d/%d - Loss: %.6f - Time %.2f sec' % (itr, self.num_iter_fit, avg_loss.item(), duration)
-                    self._check_numerics()
-                    self._g_cum.zero_()
-                    t = time.time()
-                    if valid_tuples is not None:
-                        valid_ll, valid_rmse, calibr_err = self.eval_datasets(valid_tuples)
-                        message += ' - Valid-LL: %.3f - Valid-RMSE: %.3f - Calib-Err %.3f' % (valid_ll, valid_rmse, calibr_err)
-                    self._last_log = message
-                    if verbose:
-                        self.logger.info(message)
-            if n_iter > 0:
+
+            def avg_loss(itr):                            # (the loss summed since the last line, over log_period)
+                avg = (self._g_cum / (log_period if itr > 1 else 1.0)).item()
+                self._g_cum.zero_()
+                return avg
+            if self._fit_loop(n_iter, log_period, valid_tuples, verbose, self._train_steps, avg_loss) > 0:
                 loss_val = self._g_loss.item()
             self._check_numerics()
         else:
@@ -336,25 +262,9 @@ class GPRegressionMetaLearned(RegressionModelMetaLearned):
         self.fitted = True
         return loss_val
 
-    def _check_numerics(self):
-        """raise where the reference raises: gpytorch's psd_safe_cholesky -> NotPSDError (read at synchronisation points only)"""
-        flag = getattr(self, '_fail', None)
-        bad = flag is not None and int(flag.item()) != 0
-        if not bad and parallel.world()[1] > 1 and getattr(self, '_g_loss', None) is not None:
-            bad = not bool(torch.isfinite(self._g_loss).all())    # another rank's shard failed: its NaN loss came through the all-reduce
-        if bad:
-            if flag is not None:
-                flag.zero_()
-            raise NotPSDError('a task kernel matrix was not positive definite even after adding jitter (1e-6 .. 1e-4)')
-
     def predict(self, context_x, context_y, test_x, return_density=False):
         """GPR_meta_mll.py:149-190 -> (pred_mean, pred_std) numpy, or the predictive distribution."""
-        cx, cy, tx = self._prepare_predict(context_x, context_y, test_x)
-        mu, var, cov, _ = self.engine.predict(self.theta, cx, cy, tx, want_cov=return_density)
-        dist = GaussianPredictive(mu, var, cov, self.y_mean.reshape(-1)[0], self.y_std.reshape(-1)[0], mixture=False)
-        if return_density:
-            return dist
-        return dist.mean.cpu().numpy(), dist.stddev.cpu().numpy()
+        return self._predictive(self.theta, context_x, context_y, test_x, return_density, mixture=False)
 
     def _eval_params(self, **kwargs):
         return (self.theta, False, False) if not kwargs else None

@@ -3,7 +3,6 @@ One svgd_step = [MLP fwd x2] -> fused GP LML fwd+bwd over tasks x particles -> [
 hyper-prior grad -> SVGD phi -> Adam, all HIP kernels on one stream; with torch.distributed
 initialised, tasks are sharded over ranks and the score is all-reduced once per step (RCCL)."""
 import os
-import time
 
 import numpy as np
 import torch
@@ -11,9 +10,7 @@ import torch
 from . import _lib as L
 from . import parallel
 from .abstract import RegressionModelMetaLearned
-from .distributions import GaussianPredictive
-from .engine import (AsyncUploader, GPEngine, NotPSDError, ParamLayout, StepFeed, StepMode, TaskBatch, build_step_graphs,
-                     first_chunk, replay_steps, run_step)
+from .engine import AsyncUploader, GPEngine, ParamLayout, StepDriver, StepMode, TaskBatch
 from .util import StepLR
 
 
@@ -51,7 +48,7 @@ def harmonic_pre_factor(sizes):
     return float(hm / (hm + np.float32(len(sizes))))
 
 
-class _RandomGPLearner(RegressionModelMetaLearned):
+class _RandomGPLearner(StepDriver, RegressionModelMetaLearned):
     """what SVGD and VI share: RandomGPMeta semantics (random_gp.py:116-222) on the device engine"""
 
     def _setup_random_gp(self, meta_train_data, mean_module, covar_module, mean_nn_layers, kernel_nn_layers,
@@ -79,11 +76,6 @@ class _RandomGPLearner(RegressionModelMetaLearned):
         tasks = [self._prepare_data_per_task(x, y) for x, y in meta_train_data]
         self.tasks = TaskBatch(tasks, self.device, self.dtype)
 
-    def _take_idx(self, k):
-        """the next k global task draws, int64 [k, B]: one randint call of shape [k, B] consumes the numpy stream exactly like k calls
-        of size B (GPR_meta_svgd.py:102 draws one batch per iteration)"""
-        return self.rds_numpy.randint(0, self.tasks.T, size=(k, self.task_batch_size))
-
     def _sample_task_batch(self):
         """global with-replacement draw from the shared seed (GPR_meta_svgd.py:102), then this rank's shard"""
         idx = self._take_idx(1)[0]
@@ -97,22 +89,8 @@ class _RandomGPLearner(RegressionModelMetaLearned):
     # pre-factor, learning rate, Adam's bias corrections) from device buffers filled for up to GRAPH_CHUNK steps at once
     # (engine.StepFeed), so the launch sequence is captured once and replayed.  With several ranks the step is two graphs around
     # the eager all-reduce of the packed score buffer.  PACOH_NO_GRAPH=1 runs the very same launch sequence eagerly.
-    GRAPH_CHUNK = 1024
-
-    def _graphs_allowed(self):
-        return (os.environ.get('PACOH_NO_GRAPH', '0') != '1' and self.tasks.n <= L.gp_small_max_n(self.dtype, True)
-                and not L.FORCE_DENSE)
-
-    def _local_batch_size(self):
-        return len(parallel.shard(np.arange(self.task_batch_size)))
-
-    def _draw_steps(self, k, lr_scheduler, first_step, weight_decay=0.0):
-        """task draws (this rank's shard) and step scalars of the next k steps, vectorised: one randint call of shape [k, B] consumes
-        the numpy stream exactly like k calls of size B (GPR_meta_svgd.py:102 draws one batch per iteration)"""
-        return self._rows_to_feed(self._take_idx(k), lr_scheduler, first_step, weight_decay)
-
-    def _rows_to_feed(self, idx, lr_scheduler, first_step, weight_decay=0.0):
-        """task draws idx [k, B] -> (this rank's shard of them, the steps' scalar rows)"""
+    def _step_scalars(self, idx):
+        """the steps' scalar rows of the task draws idx [k, B]"""
         k = idx.shape[0]
         # harmonic pre-factor per step (random_gp.py:209-212); tasks of one size: every row is the same computation on the same
         # numbers -- done once
@@ -122,11 +100,7 @@ class _RandomGPLearner(RegressionModelMetaLearned):
         pre = (hm / (hm + np.float32(self.task_batch_size))).astype(np.float64)
         if not self.tasks.ragged:
             pre = np.repeat(pre, k)
-        sc_rows = L.step_scalar_rows(pre, lr_scheduler.lrs(k), first_step, weight_decay=weight_decay)
-        rank, world = parallel.world()
-        local = np.ascontiguousarray(idx[:, rank::world])
-        parallel.check_same_draws(local, sc_rows)
-        return (local if local.shape[1] > 0 else None), sc_rows
+        return L.step_scalar_rows(pre, self.lr_scheduler.lrs(k), self.opt_step + 1)
 
     # Under-filled grids (round 6): the reference's own launchers run 2 tasks x 10 particles / samples of 20 points per step -- 20 GP
     # problems, for which networks forward -> GP -> networks backward -> slab reduction are four kernel latencies.  There the
@@ -148,19 +122,6 @@ class _RandomGPLearner(RegressionModelMetaLearned):
         if ws is not None:
             self._task_plan, self._task_ws = plan, ws
         return ws
-
-    def _check_numerics(self):
-        """raise where the reference raises: gpytorch's psd_safe_cholesky -> NotPSDError (read at synchronisation points only)"""
-        flag = getattr(self, '_fail', None)
-        bad = flag is not None and int(flag.item()) != 0
-        if not bad and parallel.world()[1] > 1 and getattr(self, '_lik', None) is not None:
-            # another rank's shard failed: its NaN likelihood sums reach every rank through the all-reduce, so that all ranks raise
-            # at the same synchronisation point (a rank raising alone would leave the others waiting in the next collective)
-            bad = not bool(torch.isfinite(self._lik).all())
-        if bad:
-            if flag is not None:
-                flag.zero_()
-            raise NotPSDError('a task kernel matrix was not positive definite even after adding jitter (1e-6 .. 1e-4)')
 
     def _idx_uploader(self):
         up = getattr(self, '_idx_up', None)
@@ -185,14 +146,6 @@ class _RandomGPLearner(RegressionModelMetaLearned):
         logprior = L.prior_logprob_grad(theta, self.prior_mean, self.prior_std, score, self.prior_factor)
         L.axpy(lik, logprior, self.prior_factor)                      # lik += prior_factor * log p(theta)
         return lik, score
-
-    def _mixture_predict(self, theta, context_x, context_y, test_x, return_density, mixture=True):
-        cx, cy, tx = self._prepare_predict(context_x, context_y, test_x)
-        mu, var, cov, _ = self.engine.predict(theta, cx, cy, tx, want_cov=return_density)
-        dist = GaussianPredictive(mu, var, cov, self.y_mean.reshape(-1)[0], self.y_std.reshape(-1)[0], mixture=mixture)
-        if return_density:
-            return dist
-        return dist.mean.cpu().numpy(), dist.stddev.cpu().numpy()
 
 
 class GPRegressionMetaLearnedSVGD(_RandomGPLearner):
@@ -223,22 +176,20 @@ class GPRegressionMetaLearnedSVGD(_RandomGPLearner):
         self.opt_step = 0
         self.lr_scheduler = StepLR(lr, 1000, lr_decay)
         self._svgd_ws = None
-        self._feed = self._graphs = None
         self._step_mode = StepMode()
         self._setup_tasks(meta_train_data)
         self.fitted = False
 
     # ---- one SVGD step = likelihood body -> [all-reduce] -> update body ----------------------------------------------------------
+    _STEP_STATE = ('particles', 'exp_avg', 'exp_avg_sq')
+
     def _setup_step(self, tb_local):
-        if getattr(self, '_feed', None) is not None and self._feed.tb == tb_local:
+        if self._feed is not None and self._feed.tb == tb_local:
             return
         P, D = self.particles.shape
-        self._packed, self._score, self._lik = parallel.packed_score_buffer(P, D, self.dtype, self.device)
-        self._fail = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._score, self._lik = self._new_step(tb_local, P, self.GRAPH_CHUNK)      # score [P, D] | lik [P]
         self._bw_out = torch.zeros(1, dtype=self.dtype, device=self.device)
-        self._feed = StepFeed(self.device, self.dtype, tb_local, chunk=self.GRAPH_CHUNK)
         self._svgd_ws = L.svgd_update_workspace(self.particles, self._svgd_ws)
-        self._graphs = None
         # Five launches per step instead of six (csrc/step_tail.h): the distance matrix rides in the forward launch, the next step's
         # scalars and task batch are fetched by the update launch.  A rank without tasks of its own has no forward launch: it keeps
         # the step_begin launch.  PACOH_SVGD_PIPELINE=0: the round-2 launch sequence (A/B measurements, bit-identity tests)
@@ -315,87 +266,25 @@ class GPRegressionMetaLearnedSVGD(_RandomGPLearner):
             L.scale_dev(neg_phi, sc[L.SC_LR:L.SC_LR + 1])          # particles -= lr * (-phi)
             L.axpy(self.particles, neg_phi, -1.0)
 
-    def _exchange(self):
-        parallel.all_reduce_buffer_(self._packed)         # ONE exchange per step: score [P, D] | lik [P], in place
-
-    def _build_graphs(self):
-        state = (self.particles, self.exp_avg, self.exp_avg_sq, self._feed.ctr, self._fail)
-        saved = [t.clone() for t in state]
-        # (the large-context path allocates O(tasks x n^2) scratch per step inside the graph's pool: one step per graph there)
-        self._graphs, self._graph_many = build_step_graphs(self._body_likelihood, self._exchange, self._body_update, self._feed,
-                                                           many_ok=self.tasks.n <= 128)
-        for t, sv in zip(state, saved):
-            t.copy_(sv)                                   # undo what the warm-up runs did
-        if self._pipelined:
-            self._feed.prologue()                         # (batch buffers, scalars and hyper-parameters of the restored particles)
-
-    def _run_step(self, graphed):
-        run_step(self._graphs, graphed, self._body_likelihood, self._exchange, self._body_update)
-
-    def _train_steps(self, n_steps):
-        """the next n_steps SVGD steps of the training loop (task draws from rds_numpy, lr from the scheduler)"""
-        self._setup_step(self._local_batch_size())
-        graphed = self._graphs_allowed()
-        ramp = True
-        while n_steps > 0:
-            k = first_chunk(n_steps, self.GRAPH_CHUNK) if ramp else min(n_steps, self.GRAPH_CHUNK)
-            ramp = False
-            idx_rows, sc_rows = self._draw_steps(k, self.lr_scheduler, self.opt_step + 1)
-            self._feed.upload(idx_rows, sc_rows)
-            if self._pipelined:
-                self._feed.prologue()
-            if graphed and self._graphs is None:
-                self._build_graphs()                      # (captured with real operands in the feed; state and counter are restored)
-            if graphed:
-                # replay or eager launches, whichever is faster here (engine.StepMode); several steps per replay where possible
-                many = (lambda n: replay_steps(n, self._graphs[0], self._graph_many)) if len(self._graphs) == 1 else None
-                self._step_mode.run(k, self._run_step, many)
-            else:
-                for _ in range(k):
-                    self._run_step(False)
-            self.opt_step += k
-            for _ in range(k):
-                self.lr_scheduler.step()
-            n_steps -= k
-
     def svgd_step(self, idx_local, pre_factor):
         """SVGD.step (meta_learn/svgd.py:25-28) on an explicit task draw: particles.grad = -phi; optimizer.step()"""
         self._setup_step(len(idx_local))
         self.opt_step += 1
         self._feed.upload(np.asarray(idx_local).reshape(1, -1) if len(idx_local) > 0 else None,
                           [L.step_scalars(pre_factor, self.lr_scheduler.lr, self.opt_step)])
-        if self._pipelined:
-            self._feed.prologue()
+        self._prologue()
         self._run_step(False)
 
     def meta_fit(self, valid_tuples=None, verbose=True, log_period=500, n_iter=None):
         """GPR_meta_svgd.py:82-121"""
         assert (valid_tuples is None) or (all([len(valid_tuple) == 4 for valid_tuple in valid_tuples]))
-        t = time.time()
-        if n_iter is None:
-            n_iter = self.num_iter_fit
-        itr = 0
-        while itr < n_iter:
-            nxt = 1 if itr == 0 else min(n_iter, (itr // log_period + 1) * log_period)      # up to the next log line
-            self._train_steps(nxt - itr)                  # (both particle kernels: steps replayed from captured graphs)
-            itr = nxt
-            if itr == 1 or itr % log_period == 0:
-                torch.cuda.synchronize()
-                self._check_numerics()
-                duration = time.time() - t
-                t = time.time()
-                message = 'Iter %d/%d - Time %.2f sec' % (itr, self.num_iter_fit, duration)
-                if valid_tuples is not None:
-                    valid_ll, valid_rmse, calibr_err = self.eval_datasets(valid_tuples)
-                    message += ' - Valid-LL: %.3f - Valid-RMSE: %.3f - Calib-Err %.3f' % (valid_ll, valid_rmse, calibr_err)
-                if verbose:
-                    self.logger.info(message)
+        self._fit_loop(n_iter, log_period, valid_tuples, verbose, self._train_steps)
         self._check_numerics()
         self.fitted = True
 
     def predict(self, context_x, context_y, test_x, return_density=False):
         """GPR_meta_svgd.py:123-159: equal-weighted mixture over the particles' GP posteriors"""
-        return self._mixture_predict(self.particles, context_x, context_y, test_x, return_density)
+        return self._predictive(self.particles, context_x, context_y, test_x, return_density)
 
     def _eval_params(self, **kwargs):
         return (self.particles, True, False) if not kwargs else None

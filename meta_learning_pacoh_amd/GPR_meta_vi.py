@@ -7,13 +7,11 @@ ELBO gradient needs only the per-sample score from the device engine:
   dloss/dL_ij = -mean_s score_si eps_sj - [i == j] prior_factor / L_ii   (j <= i; zero above the diagonal)."""
 import math
 import os
-import time
 
 import torch
 
 from . import _lib as L
-from . import parallel
-from .engine import AsyncUploader, StepFeed, StepMode, build_step_graphs, first_chunk, replay_steps, run_step
+from .engine import AsyncUploader, StepMode, first_chunk
 from .GPR_meta_svgd import _RandomGPLearner
 from .util import StepLR
 
@@ -82,7 +80,6 @@ class GPRegressionMetaLearnedVI(_RandomGPLearner):
         self.exp_avg_sq = torch.zeros_like(self.posterior)
         self.opt_step = 0
         self.lr_scheduler = StepLR(lr, 1000, lr_decay)
-        self._feed = self._graphs = None
         self._step_mode = StepMode()
         self._setup_tasks(meta_train_data)
         self.fitted = False
@@ -120,20 +117,19 @@ class GPRegressionMetaLearnedVI(_RandomGPLearner):
         return loss, L.vi_grad(self.posterior, eps, score, self.prior_factor, full=self.cov_type == 'full')
 
     # ---- one VI step as hipGraph(s): sample + likelihood score -> [all-reduce] -> ELBO gradient + Adam ---------------------------
+    _STEP_STATE = ('posterior', 'exp_avg', 'exp_avg_sq')
+
     def _setup_step(self, tb_local):
-        if getattr(self, '_feed', None) is not None and self._feed.tb == tb_local:
+        if self._feed is not None and self._feed.tb == tb_local:
             return
         S, D = self.svi_batch_size, self.layout.D
-        self._packed, self._score, self._lik = parallel.packed_score_buffer(S, D, self.dtype, self.device)
-        self._fail = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self._loss = torch.zeros((), dtype=self.dtype, device=self.device)
-        self._vi_ws = L.vi_update_workspace(self.posterior)
         # The noise of a chunk is drawn on the host, one rsample per step in the reference's stream order (0.1 ms per step at S = 10,
         # D = 2.5 k): chunks of 128 steps, so that drawing chunk k+1 overlaps the GPU running chunk k instead of preceding it
         # (measured at cfg #4, 200-step calls: one chunk 0.577 ms per step, 128-step chunks 0.52-0.55, 64-step chunks 0.62)
         chunk = max(1, min(self.GRAPH_CHUNK, int(os.environ.get('PACOH_VI_CHUNK', '128')), (64 << 20) // (S * D * 4)))
-        self._feed = StepFeed(self.device, self.dtype, tb_local, chunk=chunk, aux_shape=(S, D))
-        self._graphs = None
+        self._score, self._lik = self._new_step(tb_local, S, chunk, aux_shape=(S, D))      # score [S, D] | lik [S]
+        self._loss = torch.zeros((), dtype=self.dtype, device=self.device)
+        self._vi_ws = L.vi_update_workspace(self.posterior)
         self._setup_task_fused(S, tb_local)              # (under-filled grids: the task-fused likelihood launch, GPR_meta_svgd.py)
 
     def _body_likelihood(self):
@@ -170,80 +166,40 @@ class GPRegressionMetaLearnedVI(_RandomGPLearner):
         L.adam_step_dev(self.posterior, grad, self.exp_avg, self.exp_avg_sq, self._feed.sc[L.SC_ADAM:L.SC_ADAM + 4],
                         step_counter=self._feed.ctr)
 
-    def _exchange(self):
-        parallel.all_reduce_buffer_(self._packed)         # ONE exchange per step: score [S, D] | lik [S], in place
+    def _chunk_size(self, n_steps, last):
+        # chunk sizes 16, 24, 36, 52, ...: the host draws 0.15-0.19 ms of noise per step, the GPU needs 0.4-0.5 ms per step -- a
+        # chunk must take the host less to prepare than the one in flight takes the GPU, or the GPU runs dry (growth 2 left a
+        # margin of 10 % on the slower hosts: cfg #4 read 0.42 or 0.49 ms per step depending on the box)
+        if last == 0:
+            return first_chunk(n_steps, self._feed.chunk)
+        return min(n_steps, self._feed.chunk, (last + last // 2 + 3) // 4 * 4)
 
-    def _build_graphs(self):
-        state = (self.posterior, self.exp_avg, self.exp_avg_sq, self._feed.ctr, self._fail)
-        saved = [t.clone() for t in state]
-        # (the large-context path allocates O(tasks x n^2) scratch per step inside the graph's pool: one step per graph there)
-        self._graphs, self._graph_many = build_step_graphs(self._body_likelihood, self._exchange, self._body_update, self._feed,
-                                                           many_ok=self.tasks.n <= 128)
-        for t, sv in zip(state, saved):
-            t.copy_(sv)
-
-    def _run_step(self, graphed):
-        run_step(self._graphs, graphed, self._body_likelihood, self._exchange, self._body_update)
-
-    def _train_steps(self, n_steps):
-        self._setup_step(self._local_batch_size())
-        graphed = self._graphs_allowed()
+    def _step_payload(self):
+        # the reference's stream: one rsample per step, drawn straight into the pinned staging rows (noise='device': the chunk's
+        # rows filled by one launch of the device generator, nothing drawn or copied on the host)
+        if self.noise == 'device':
+            return 'device'
         S, D = self.svi_batch_size, self.layout.D
-        k = 0
-        while n_steps > 0:
-            # chunk sizes 16, 24, 36, 52, ...: the host draws 0.15-0.19 ms of noise per step, the GPU needs 0.4-0.5 ms per step -- a
-            # chunk must take the host less to prepare than the one in flight takes the GPU, or the GPU runs dry (growth 2 left a
-            # margin of 10 % on the slower hosts: cfg #4 read 0.42 or 0.49 ms per step depending on the box)
-            k = first_chunk(n_steps, self._feed.chunk) if k == 0 else min(n_steps, self._feed.chunk, (k + k // 2 + 3) // 4 * 4)
-            idx_rows, sc_rows = self._draw_steps(k, self.lr_scheduler, self.opt_step + 1)
-            # the reference's stream: one rsample per step, drawn straight into the pinned staging rows (noise='device': the chunk's
-            # rows filled by one launch of the device generator, nothing drawn or copied on the host)
-            self._feed.upload(idx_rows, sc_rows, 'device' if self.noise == 'device' else (lambda j, out: standard_normal(S, D, out=out)))
-            if graphed and self._graphs is None:
-                self._build_graphs()                      # (captured with real operands in the feed; state and counter are restored)
-            if graphed:
-                # replay or eager launches, whichever is faster here (engine.StepMode); several steps per replay where possible
-                many = (lambda n: replay_steps(n, self._graphs[0], self._graph_many)) if len(self._graphs) == 1 else None
-                self._step_mode.run(k, self._run_step, many)
-            else:
-                for _ in range(k):
-                    self._run_step(False)
-            self.opt_step += k
-            for _ in range(k):
-                self.lr_scheduler.step()
-            n_steps -= k
-        return self._loss
+        return lambda j, out: standard_normal(S, D, out=out)
 
     def meta_fit(self, valid_tuples=None, verbose=True, log_period=500, n_iter=None):
         """GPR_meta_vi.py:84-128"""
         assert (valid_tuples is None) or (all([len(valid_tuple) == 4 for valid_tuple in valid_tuples]))
-        t = time.time()
-        if n_iter is None:
-            n_iter = self.num_iter_fit
         loss = None
-        itr = 0
-        while itr < n_iter:
-            nxt = 1 if itr == 0 else min(n_iter, (itr // log_period + 1) * log_period)      # up to the next log line
+
+        def run(n):
+            nonlocal loss
             if self.optimizer_name == 'Adam':
-                loss = self._train_steps(nxt - itr)
-            else:
-                for _ in range(nxt - itr):
-                    idx_local, pre = self._sample_task_batch()
-                    loss, grad = self.get_neg_elbo_and_grad(idx_local, pre)
-                    self.opt_step += 1
-                    L.axpy(self.posterior, grad, -self.lr_scheduler.lr)
-                    self.lr_scheduler.step()
-            itr = nxt
-            if itr == 1 or itr % log_period == 0:
-                duration = time.time() - t
-                t = time.time()
-                message = 'Iter %d/%d - Loss: %.6f - Time %.2f sec' % (itr, self.num_iter_fit, loss.item(), duration)
-                self._check_numerics()
-                if valid_tuples is not None:
-                    valid_ll, valid_rmse, calibr_err = self.eval_datasets(valid_tuples)
-                    message += ' - Valid-LL: %.3f - Valid-RMSE: %.3f - Calib-Err %.3f' % (valid_ll, valid_rmse, calibr_err)
-                if verbose:
-                    self.logger.info(message)
+                self._train_steps(n)
+                loss = self._loss
+                return
+            for _ in range(n):
+                idx_local, pre = self._sample_task_batch()
+                loss, grad = self.get_neg_elbo_and_grad(idx_local, pre)
+                self.opt_step += 1
+                L.axpy(self.posterior, grad, -self.lr_scheduler.lr)
+                self.lr_scheduler.step()
+        self._fit_loop(n_iter, log_period, valid_tuples, verbose, run, lambda itr: loss.item())
         self.fitted = True
         out = loss.item() if loss is not None else float('nan')
         self._check_numerics()
@@ -254,9 +210,9 @@ class GPRegressionMetaLearnedVI(_RandomGPLearner):
         assert mode in ['bayes', 'Bayes', 'MAP', 'map']
         if mode in ('Bayes', 'bayes'):
             theta, _, _ = self._rsample(n_posterior_samples)
-            return self._mixture_predict(theta, context_x, context_y, test_x, return_density, mixture=True)
+            return self._predictive(theta, context_x, context_y, test_x, return_density, mixture=True)
         theta = self.loc.reshape(1, -1).contiguous()
-        return self._mixture_predict(theta, context_x, context_y, test_x, return_density, mixture=False)
+        return self._predictive(theta, context_x, context_y, test_x, return_density, mixture=False)
 
     def _eval_params(self, n_posterior_samples=100, mode='Bayes', **kwargs):
         """eval_datasets in one batched pass: predict() draws n_posterior_samples fresh parameter rows per call, so T tasks need

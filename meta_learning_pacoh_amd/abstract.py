@@ -7,6 +7,7 @@ import torch
 
 from . import _lib as L
 from .config import get_device
+from .distributions import GaussianPredictive
 from .util import _handle_input_dimensionality, get_logger
 
 
@@ -158,6 +159,16 @@ class RegressionModelMetaLearned:
         cx, cy = self._prepare_data_per_task(context_x, context_y)
         tx = self._normalize_data(X=test_x, Y=None).astype(np.float32)
         return self._to_device(cx), self._to_device(cy), self._to_device(tx)
+
+    def _predictive(self, theta, context_x, context_y, test_x, return_density, mixture=True):
+        """predict(): the GP posterior predictive of every parameter row of theta on the context -- their equal-weighted mixture, or
+        (mixture=False, one row) that row's -> the distribution, or (mean, stddev) numpy"""
+        cx, cy, tx = self._prepare_predict(context_x, context_y, test_x)
+        mu, var, cov, _ = self.engine.predict(theta, cx, cy, tx, want_cov=return_density)
+        dist = GaussianPredictive(mu, var, cov, self.y_mean.reshape(-1)[0], self.y_std.reshape(-1)[0], mixture=mixture)
+        if return_density:
+            return dist
+        return dist.mean.cpu().numpy(), dist.stddev.cpu().numpy()
 
 
 def _calib_error(pred_dist, test_t_tensor):

@@ -245,19 +245,8 @@ class StepFeed:
         """switch the feed to the pipelined SVGD step (csrc/step_tail.h): persistent batch buffers, transformed hyper-parameters and
         two rows of step scalars, filled one step ahead by the update launch.  prologue() after every upload()"""
         assert self.tb > 0
-        dev, dt = tasks.x.device, tasks.x.dtype
-        batch = TaskBatch.__new__(TaskBatch)
-        batch.T, batch.n, batch.ragged, batch.sizes = self.tb, tasks.n, tasks.ragged, None
-        batch.x = torch.empty(self.tb, tasks.n, tasks.x.shape[2], dtype=dt, device=dev)
-        batch.y = torch.empty(self.tb, tasks.n, dtype=dt, device=dev)
-        batch.n_valid = torch.empty(self.tb, dtype=torch.int32, device=dev) if tasks.ragged else None
-        off_ls, f, off_os, off_noise, _ = engine._hyper_offsets()
-        P = theta.shape[0]
-        self.batch = batch
-        self.hyp = (torch.empty(P, f, dtype=theta.dtype, device=theta.device),
-                    torch.empty(P, dtype=theta.dtype, device=theta.device) if off_os >= 0 else None,
-                    torch.empty(P, dtype=theta.dtype, device=theta.device))
-        self.hyper = (off_ls, f, off_os, off_noise, engine.noise_floor, engine.layout.kernel_code)
+        self.batch = self._empty_batch(tasks)
+        self.hyper, self.hyp = self._hyper_buffers(engine, theta.shape[0], theta)
         self.sc2 = torch.zeros(2, L.SC_COUNT, dtype=self.dtype, device=self.device)
         self._row0 = torch.zeros(1, dtype=torch.int64, device=self.device)      # constant: the prologue works on row 0
         self._pipe = (tasks, theta)
@@ -275,55 +264,50 @@ class StepFeed:
     def select(self):
         L.step_select(self.idx_all, self.sc_all, self.ctr, self.idx, self.sc, self.aux_all, self.aux)
 
+    def _empty_batch(self, tasks):
+        """the step's TaskBatch of tb tasks shaped like `tasks`, for a launch to fill (None on a rank without tasks)"""
+        if self.tb == 0:
+            return None
+        dev, dt = tasks.x.device, tasks.x.dtype
+        batch = TaskBatch.__new__(TaskBatch)
+        batch.T, batch.n, batch.ragged, batch.sizes = self.tb, tasks.n, tasks.ragged, None
+        batch.x = torch.empty(self.tb, tasks.n, tasks.x.shape[2], dtype=dt, device=dev)
+        batch.y = torch.empty(self.tb, tasks.n, dtype=dt, device=dev)
+        batch.n_valid = torch.empty(self.tb, dtype=torch.int32, device=dev) if tasks.ragged else None
+        return batch
+
+    @staticmethod
+    def _hyper_buffers(engine, R, like):
+        """the transformed hyper-parameters of R parameter rows through `engine` (dtype and device of `like`), for a launch to fill
+        -> (the operand tuple of the transforms, (ls [R, f], outputscale [R] | None, noise [R]))"""
+        off_ls, f, off_os, off_noise, _ = engine._hyper_offsets()
+        dev, dt = like.device, like.dtype
+        hyp = (torch.empty(R, f, dtype=dt, device=dev), torch.empty(R, dtype=dt, device=dev) if off_os >= 0 else None,
+               torch.empty(R, dtype=dt, device=dev))
+        return (off_ls, f, off_os, off_noise, engine.noise_floor, engine.layout.kernel_code), hyp
+
     def begin(self, tasks, engine=None, theta=None, advance=True, svgd=None):
         """select() + the step's task gather (+ the hyper-parameter transforms of theta through `engine`, + the SVGD distance
         matrix of svgd = (particles, workspace)) in ONE launch -> (TaskBatch | None, hypers | None); advance=False: the step's
         last launch advances the counter (L.step_begin)"""
-        batch = hyp = None
-        out = None
-        if self.tb > 0:
-            batch = TaskBatch.__new__(TaskBatch)
-            batch.T, batch.n, batch.ragged, batch.sizes = self.tb, tasks.n, tasks.ragged, None
-            batch.x = torch.empty(self.tb, tasks.n, tasks.x.shape[2], dtype=tasks.x.dtype, device=tasks.x.device)
-            batch.y = torch.empty(self.tb, tasks.n, dtype=tasks.x.dtype, device=tasks.x.device)
-            batch.n_valid = torch.empty(self.tb, dtype=torch.int32, device=tasks.x.device) if tasks.ragged else None
-            out = (batch.x, batch.y, batch.n_valid)
-        hyper = hyper_out = None
-        if theta is not None and self.tb > 0:
-            off_ls, f, off_os, off_noise, _ = engine._hyper_offsets()
-            P = theta.shape[0]
-            ls = torch.empty(P, f, dtype=theta.dtype, device=theta.device)
-            os_ = torch.empty(P, dtype=theta.dtype, device=theta.device) if off_os >= 0 else None
-            noise = torch.empty(P, dtype=theta.dtype, device=theta.device)
-            hyper, hyper_out = (off_ls, f, off_os, off_noise, engine.noise_floor, engine.layout.kernel_code), (ls, os_, noise)
-            hyp = hyper_out
-        L.step_begin(self, tasks, out, theta if hyp is not None else None, hyper, hyper_out, advance=advance, svgd=svgd)
+        batch = self._empty_batch(tasks)
+        out = (batch.x, batch.y, batch.n_valid) if batch is not None else None
+        hyper = hyp = None
+        if theta is not None and batch is not None:
+            hyper, hyp = self._hyper_buffers(engine, theta.shape[0], theta)
+        L.step_begin(self, tasks, out, theta if hyp is not None else None, hyper, hyp, advance=advance, svgd=svgd)
         return batch, hyp
 
-
-def _begin_vi(self, tasks, engine, posterior, S):
-    """StepFeed.begin for a PACOH-VI step with a diagonal posterior: select (incl. the step's noise) + task gather + the step's
-    samples, their log q and transformed hyper-parameters in ONE launch -> (TaskBatch | None, hypers, theta[S, D], log_q[S])"""
-    D = posterior.shape[1]
-    dev, dt = posterior.device, posterior.dtype
-    batch = out = None
-    if self.tb > 0:
-        batch = TaskBatch.__new__(TaskBatch)
-        batch.T, batch.n, batch.ragged, batch.sizes = self.tb, tasks.n, tasks.ragged, None
-        batch.x = torch.empty(self.tb, tasks.n, tasks.x.shape[2], dtype=tasks.x.dtype, device=tasks.x.device)
-        batch.y = torch.empty(self.tb, tasks.n, dtype=tasks.x.dtype, device=tasks.x.device)
-        batch.n_valid = torch.empty(self.tb, dtype=torch.int32, device=tasks.x.device) if tasks.ragged else None
-        out = (batch.x, batch.y, batch.n_valid)
-    off_ls, f, off_os, off_noise, _ = engine._hyper_offsets()
-    hyp = (torch.empty(S, f, dtype=dt, device=dev), torch.empty(S, dtype=dt, device=dev) if off_os >= 0 else None,
-           torch.empty(S, dtype=dt, device=dev))
-    theta, log_q = torch.empty(S, D, dtype=dt, device=dev), torch.empty(S, dtype=dt, device=dev)
-    L.step_begin_vi(self, tasks, out, posterior, theta, log_q, (off_ls, f, off_os, off_noise, engine.noise_floor, engine.layout.kernel_code),
-                    hyp, advance=False)
-    return batch, hyp, theta, log_q
-
-
-StepFeed.begin_vi = _begin_vi
+    def begin_vi(self, tasks, engine, posterior, S):
+        """begin() for a PACOH-VI step with a diagonal posterior: select (incl. the step's noise) + task gather + the step's S
+        samples, their log q and transformed hyper-parameters in ONE launch -> (TaskBatch | None, hypers, theta[S, D], log_q[S])"""
+        batch = self._empty_batch(tasks)
+        out = (batch.x, batch.y, batch.n_valid) if batch is not None else None
+        hyper, hyp = self._hyper_buffers(engine, S, posterior)
+        theta = torch.empty(S, posterior.shape[1], dtype=posterior.dtype, device=posterior.device)
+        log_q = torch.empty(S, dtype=posterior.dtype, device=posterior.device)
+        L.step_begin_vi(self, tasks, out, posterior, theta, log_q, hyper, hyp, advance=False)
+        return batch, hyp, theta, log_q
 
 
 GRAPH_STEPS = 4      # steps per graph of the second graph the learners capture at world size 1 (hipGraphLaunch costs the host per
@@ -377,45 +361,6 @@ def capture_graph(body, warmup=2, before=None):
         with torch.cuda.graph(graph, **kw):
             body()
     return graph
-
-
-def build_step_graphs(body_likelihood, exchange, body_update, feed, many_ok=True):
-    """the hipGraphs of one meta-training step = body_likelihood -> exchange (the all-reduce of the packed buffer) -> body_update:
-    ((whole step,), four steps) when the exchange can be captured (world size 1, or RCCL on the compute stream:
-    parallel.collective_in_graph()), else ((likelihood, update), None) around the eager torch.distributed call"""
-    def rewind():
-        if feed.sc2 is not None:
-            feed.ctr.fill_(-1)                            # pipelined SVGD step: row 0 fetched again, counter = -1
-            feed.prologue()
-        else:
-            feed.ctr.zero_()
-    if parallel.collective_in_graph():
-        def whole():
-            body_likelihood()
-            exchange()
-            body_update()
-
-        def several():
-            for _ in range(GRAPH_STEPS):
-                whole()
-        return (capture_graph(whole, before=rewind),), (capture_graph(several, before=rewind) if many_ok else None)
-    return (capture_graph(body_likelihood, before=rewind), capture_graph(body_update, before=rewind)), None
-
-
-def run_step(graphs, graphed, body_likelihood, exchange, body_update):
-    """one step: replayed from build_step_graphs()'s graphs, or the same launches issued one by one"""
-    if graphed:
-        graphs[0].replay()
-        if len(graphs) > 1:
-            exchange()
-            graphs[1].replay()
-    else:
-        with L.roctx_range('likelihood'):                  # (no-ops unless PACOH_ROCTX=1)
-            body_likelihood()
-        with L.roctx_range('exchange'):
-            exchange()
-        with L.roctx_range('update'):
-            body_update()
 
 
 class StepMode:
@@ -497,6 +442,194 @@ class StepMode:
             for _ in range(n_steps - done):
                 step(graphed)
         self._since += n_steps
+
+
+class StepDriver:
+    """The training loop the meta-learners share: their steps are drawn and uploaded in chunks (StepFeed), captured once as
+    hipGraphs and replayed, or issued launch by launch (StepMode decides; both give the same bits).  A learner provides
+    _setup_step(tb_local) (its buffers: _new_step), _body_likelihood / _body_update (the launches before and after the step's one
+    all-reduce, _exchange), _step_scalars (the rows L.step_scalar_rows makes for a chunk's task draws), and where it differs from
+    the defaults below: the chunk sizes, the per-step payload of the feed, the work of a chunk"""
+    GRAPH_CHUNK = 1024
+    _STEP_STATE = ()             # names of the learner's tensors a step changes (parameters, optimizer state): restored after a capture
+    _feed = _graphs = _graph_many = None
+    _pipelined = False
+
+    # ---- the step's buffers -------------------------------------------------------------------------------------------------------
+    def _local_batch_size(self):
+        rank, world = parallel.world()
+        return len(range(rank, self.task_batch_size, world))          # (= len(parallel.shard(range(B))), without the array)
+
+    def _new_step(self, tb_local, rows, chunk, aux_shape=None):
+        """what every step holds: ONE all-reduce operand _packed = gradient [rows, D] | likelihood sums [rows] (zeroed), the Cholesky
+        failure flag, the feed of tb_local tasks per step; no graphs yet -> (gradient view, sums view)"""
+        self._packed, grad, sums = parallel.packed_score_buffer(rows, self.layout.D, self.dtype, self.device)
+        self._packed.zero_()
+        self._fail = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._feed = StepFeed(self.device, self.dtype, tb_local, chunk=chunk, aux_shape=aux_shape)
+        self._graphs = self._graph_many = None
+        return grad, sums
+
+    def _exchange(self):
+        parallel.all_reduce_buffer_(self._packed)         # ONE exchange per step, in place
+
+    # ---- the task draws of a chunk ----------------------------------------------------------------------------------------------
+    def _take_idx(self, k):
+        """the next k global task draws, int64 [k, B]: with replacement (the reference's rds_numpy.choice / randint per iteration);
+        one randint call of shape [k, B] consumes the numpy stream exactly like k calls of size B"""
+        return self.rds_numpy.randint(0, self.tasks.T, size=(k, self.task_batch_size))
+
+    def _draw_steps(self, k):
+        """this rank's shard of the next k steps' task draws (None where it has no tasks) and the steps' scalar rows"""
+        idx = self._take_idx(k)
+        sc_rows = self._step_scalars(idx)
+        rank, world = parallel.world()
+        local = np.ascontiguousarray(idx[:, rank::world])
+        parallel.check_same_draws(local, sc_rows)
+        return (local if local.shape[1] > 0 else None), sc_rows
+
+    def _step_payload(self):
+        """the feed's per-step payload of the next chunk (StepFeed.upload's aux_rows)"""
+        return None
+
+    def _chunk_size(self, n_steps, last):
+        """steps in the next chunk of a training call with n_steps left; last: the previous chunk's size (0: the call's first)"""
+        return first_chunk(n_steps, self._feed.chunk) if last == 0 else min(n_steps, self._feed.chunk)
+
+    # ---- graphs and steps -------------------------------------------------------------------------------------------------------
+    def _graphs_allowed(self):
+        # (large contexts run the HBM-resident path, whose launch sequence sets kernel attributes: keep it eager)
+        return (os.environ.get('PACOH_NO_GRAPH', '0') != '1' and self.tasks.n <= L.gp_small_max_n(self.dtype, True)
+                and not L.FORCE_DENSE)
+
+    def _prologue(self):
+        """once per uploaded chunk, outside the step: the pipelined step's first row and hyper-parameters"""
+        if self._pipelined:
+            self._feed.prologue()
+
+    def _build_graphs(self):
+        """the hipGraphs of one step = _body_likelihood -> _exchange -> _body_update: ((whole step,), four steps) when the exchange
+        can be captured (world size 1, or RCCL on the compute stream: parallel.collective_in_graph()), else ((likelihood, update),
+        None) around the eager torch.distributed call.  Captured with real operands in the feed; the state the warm-up and capture
+        runs change is restored"""
+        feed = self._feed
+        state = [getattr(self, name) for name in self._STEP_STATE] + [feed.ctr, self._fail]
+        saved = [t.clone() for t in state]
+
+        def rewind():
+            if feed.sc2 is not None:
+                feed.ctr.fill_(-1)                        # pipelined step: row 0 fetched again, counter = -1
+                feed.prologue()
+            else:
+                feed.ctr.zero_()
+        if parallel.collective_in_graph():
+            def whole():
+                self._body_likelihood()
+                self._exchange()
+                self._body_update()
+
+            def several():
+                for _ in range(GRAPH_STEPS):
+                    whole()
+            # (the large-context path allocates O(tasks x n^2) scratch per step inside the graph's pool: one step per graph there)
+            self._graphs = (capture_graph(whole, before=rewind),)
+            self._graph_many = capture_graph(several, before=rewind) if self.tasks.n <= 128 else None
+        else:
+            self._graphs = (capture_graph(self._body_likelihood, before=rewind), capture_graph(self._body_update, before=rewind))
+            self._graph_many = None
+        for t, sv in zip(state, saved):
+            t.copy_(sv)
+        self._prologue()                                  # (of the restored state)
+
+    def _run_step(self, graphed):
+        """one step: replayed from the captured graphs, or the same launches issued one by one"""
+        if graphed:
+            self._graphs[0].replay()
+            if len(self._graphs) > 1:
+                self._exchange()
+                self._graphs[1].replay()
+        else:
+            with L.roctx_range('likelihood'):              # (no-ops unless PACOH_ROCTX=1)
+                self._body_likelihood()
+            with L.roctx_range('exchange'):
+                self._exchange()
+            with L.roctx_range('update'):
+                self._body_update()
+
+    def _run_chunk(self, k, graphed):
+        """the uploaded chunk's k steps"""
+        self._prologue()
+        if graphed and self._graphs is None:
+            self._build_graphs()
+        if graphed:
+            # replay or eager launches, whichever is faster here (StepMode); several steps per replay where possible
+            many = (lambda n: replay_steps(n, self._graphs[0], self._graph_many)) if len(self._graphs) == 1 else None
+            self._step_mode.run(k, self._run_step, many)
+        else:
+            for _ in range(k):
+                self._run_step(False)
+
+    def _train_steps(self, n_steps):
+        """the next n_steps steps of the training loop (task draws from rds_numpy, learning rates from the scheduler), in chunks:
+        the host draws and uploads chunk k + 1 while the GPU runs chunk k"""
+        self._setup_step(self._local_batch_size())
+        graphed = self._graphs_allowed()
+        k = 0
+        while n_steps > 0:
+            k = self._chunk_size(n_steps, k)
+            idx_rows, sc_rows = self._draw_steps(k)
+            self._feed.upload(idx_rows, sc_rows, self._step_payload())
+            self._run_chunk(k, graphed)
+            self.opt_step += k
+            for _ in range(k):
+                self.lr_scheduler.step()
+            n_steps -= k
+
+    # ---- meta_fit ---------------------------------------------------------------------------------------------------------------
+    def _check_numerics(self):
+        """raise where the reference raises: gpytorch's psd_safe_cholesky -> NotPSDError (read at synchronisation points only)"""
+        flag = getattr(self, '_fail', None)
+        bad = flag is not None and int(flag.item()) != 0
+        # the all-reduced sums that turn non-finite when another rank's Cholesky failed: SVGD's / VI's likelihood sums, MAP's loss
+        reduced = getattr(self, '_lik', None)
+        if reduced is None:
+            reduced = getattr(self, '_g_loss', None)
+        if not bad and parallel.world()[1] > 1 and reduced is not None:
+            # another rank's shard failed: its NaN likelihood sums reach every rank through the all-reduce, so that all ranks raise
+            # at the same synchronisation point (a rank raising alone would leave the others waiting in the next collective)
+            bad = not bool(torch.isfinite(reduced).all())
+        if bad:
+            if flag is not None:
+                flag.zero_()
+            raise NotPSDError('a task kernel matrix was not positive definite even after adding jitter (1e-6 .. 1e-4)')
+
+    def _fit_loop(self, n_iter, log_period, valid_tuples, verbose, run, loss=None):
+        """meta_fit's iterations (GPR_meta_*.py): run(n) performs the next n; a line is logged after the first one and then every
+        log_period -- with loss(itr) if given and the validation metrics of valid_tuples if given -> n_iter"""
+        if n_iter is None:
+            n_iter = self.num_iter_fit
+        t = time.time()
+        itr = 0
+        while itr < n_iter:
+            nxt = 1 if itr == 0 else min(n_iter, (itr // log_period + 1) * log_period)      # up to the next log line
+            run(nxt - itr)
+            itr = nxt
+            if itr == 1 or itr % log_period == 0:
+                torch.cuda.synchronize()
+                duration = time.time() - t
+                message = 'Iter %d/%d' % (itr, self.num_iter_fit)
+                if loss is not None:
+                    message += ' - Loss: %.6f' % loss(itr)
+                message += ' - Time %.2f sec' % duration
+                self._check_numerics()
+                t = time.time()
+                if valid_tuples is not None:
+                    valid_ll, valid_rmse, calibr_err = self.eval_datasets(valid_tuples)
+                    message += ' - Valid-LL: %.3f - Valid-RMSE: %.3f - Calib-Err %.3f' % (valid_ll, valid_rmse, calibr_err)
+                self._last_log = message
+                if verbose:
+                    self.logger.info(message)
+        return n_iter
 
 
 class NotPSDError(RuntimeError):

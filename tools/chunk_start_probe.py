@@ -26,7 +26,7 @@ for idle_ms in (0.0, 0.0, 1.0, 5.0, 20.0, 0.0):
         time.sleep(idle_ms * 1e-3)
     e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
     t0 = time.perf_counter()
-    idx_rows, sc_rows = model._draw_steps(K, model.lr_scheduler, model.opt_step + 1)
+    idx_rows, sc_rows = model._draw_steps(K)
     t1 = time.perf_counter()
     e0.record()
     model._feed.upload(idx_rows, sc_rows)

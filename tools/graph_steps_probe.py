@@ -18,7 +18,7 @@ N = 480
 
 
 def upload():
-    idx_rows, sc_rows = model._draw_steps(N, model.lr_scheduler, model.opt_step + 1)
+    idx_rows, sc_rows = model._draw_steps(N)
     model._feed.upload(idx_rows, sc_rows)
 
 
