@@ -21,6 +21,14 @@ headline metric is config 3).  Prints ONE JSON line on rank 0.
 --dump-outputs DIR: rank 0 writes what the last timed step computed (the learner's parameters and optimizer state after it, the
 step's likelihood / loss; cfg #5: the LML and its gradients) as DIR/<name>.npy, for comparing two builds output for output.  The
 warm-up then always runs its longest length, so that the timed steps start from the same state in every run.
+
+A plain run does only what the headline needs: set up, warm up, time --steps steps, [--dump-outputs], print the line.  --full adds
+everything else, each in the same process after the timed steps: the `steady` region, the eager per-kernel pass with the rooflines
+built on it, at N > 1 the other scaling leg and `all_reduce_us`, and on the default N = 1 run the standalone Gram leg, the other
+configurations (`other_configs`, each with its own CPU baseline), the posterior predictive and the CPU baseline of config 3
+(--no-other-configs / --no-cpu-baseline leave those out again).  Keys a plain run does not measure are null in its line.
+
+    python bench.py --gpus 1 --full
 """
 import argparse
 import json
@@ -158,8 +166,14 @@ def assemble_line(metric, value, world, steps, warmup, ms_per_step, scaling, dty
                   step_mode, config, roofline, kernel_rooflines, step_flops, gram, pp, others, cpu):
     """the ONE JSON line of the driver's contract (tests/test_host_logic.py asserts its shape without a GPU).  At N > 1 on the
     headline configuration `legs` holds both scaling modes -- {'weak': {...}, 'strong': {...}}, each with ms_per_step, value,
-    exchange, world_size_seen, all_reduce_us -- and the top-level value / ms_per_step are those of the `scaling` leg"""
+    exchange, world_size_seen, all_reduce_us -- and the top-level value / ms_per_step are those of the `scaling` leg.  pp and
+    step_flops are None in a plain run (no --full: no per-kernel pass), and so are the keys built on them"""
+    if pp is None:
+        pp = {'kernel_sum': None, 'ms_per_step': None, 'kernel_ms': None, 'kernel_ms_raw': None, 'event_overhead_ms': None}
     kernel_sum, prof_ms = pp['kernel_sum'], pp['ms_per_step']
+
+    def r4(v):
+        return None if v is None else round(v, 4)
     return {
         'metric': metric,
         'value': round(value, 1), 'unit': 'evals/s', 'n_gpus': world, 'steps': steps, 'warmup': warmup,
@@ -171,7 +185,7 @@ def assemble_line(metric, value, world, steps, warmup, ms_per_step, scaling, dty
         'host_ms_per_step': round(host_ms, 4), 'step_mode': step_mode,
         'config': config,
         'roofline': roofline, 'kernel_rooflines': kernel_rooflines,
-        'step_algorithmic_tflops': round(step_flops / (ms_per_step * 1e-3) / 1e12, 3),
+        'step_algorithmic_tflops': None if step_flops is None else round(step_flops / (ms_per_step * 1e-3) / 1e12, 3),
         'gram_roofline': gram,
         # per-kernel HIP-event times come from a SEPARATE pass that issues the same launch sequence eagerly (events cannot be
         # read out of a graph replay); that pass's own wall time per step is printed next to them: kernel_sum <= profile pass.
@@ -179,10 +193,11 @@ def assemble_line(metric, value, world, steps, warmup, ms_per_step, scaling, dty
         # (schema 2, round 3 on: round-2 lines carry the raw values under kernel_ms_per_step)
         'schema': 2,
         'kernel_ms_per_step': pp['kernel_ms'],
-        'kernel_ms_per_step_events_raw': pp['kernel_ms_raw'], 'event_overhead_us': round(pp['event_overhead_ms'] * 1e3, 2),
-        'kernel_sum_ms_per_step': round(kernel_sum, 4),
-        'profile_pass_ms_per_step': round(prof_ms, 4),
-        'launch_gaps_ms_per_step': round(prof_ms - kernel_sum, 4),
+        'kernel_ms_per_step_events_raw': pp['kernel_ms_raw'],
+        'event_overhead_us': None if pp['event_overhead_ms'] is None else round(pp['event_overhead_ms'] * 1e3, 2),
+        'kernel_sum_ms_per_step': r4(kernel_sum),
+        'profile_pass_ms_per_step': r4(prof_ms),
+        'launch_gaps_ms_per_step': None if kernel_sum is None else round(prof_ms - kernel_sum, 4),
         'other_configs': others,
         'cpu_baseline': cpu,
     }
@@ -195,7 +210,8 @@ def main():
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--scaling', choices=['weak', 'strong'], default='weak')
     ap.add_argument('--config', type=lambda v: int(v) if v.isdigit() else v, choices=[1, 2, 3, 4, 5, 'ref_svgd', 'ref_vi', 'shard128', 'ref_map'], default=3)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='also run every measurement beside the headline (module docstring)')
+    ap.add_argument('--no-cpu-baseline', action='store_true')      # (these two narrow --full; a plain run has neither leg)
     ap.add_argument('--no-other-configs', action='store_true')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None)
     args = ap.parse_args()
@@ -285,20 +301,22 @@ def main():
             if rank == 0:
                 dump_outputs(args.dump_outputs, wl['outputs']())
             barrier()
-        # the steady state, driver-visible: one more region of STEADY_STEPS steps right behind the --steps region (same workload, same
-        # bracketing).  The top-level value stays the --steps region's; short regions also pay the clock ramp after the idle barrier
-        # (tools/README.md), which this one dilutes.
-        t1 = time.perf_counter()
-        wl['run'](STEADY_STEPS)
-        barrier()
-        steady_s = time.perf_counter() - t1
-        if world > 1:
-            tt = torch.tensor([steady_s], dtype=torch.float64, device='cuda')
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            steady_s = float(tt.item())
-        leg = {'scaling': scaling, 'ms_per_step': round(elapsed / args.steps * 1e3, 4),
-               'steady': {'steps': STEADY_STEPS, 'ms_per_step': round(steady_s / STEADY_STEPS * 1e3, 4),
-                          'value': round(wl['evals_per_step'] * STEADY_STEPS / steady_s, 1)},
+        steady = None
+        if args.full:
+            # the steady state: one more region of STEADY_STEPS steps right behind the --steps region (same workload, same
+            # bracketing).  The top-level value stays the --steps region's; short regions also pay the clock ramp after the idle
+            # barrier (tools/README.md), which this one dilutes.
+            t1 = time.perf_counter()
+            wl['run'](STEADY_STEPS)
+            barrier()
+            steady_s = time.perf_counter() - t1
+            if world > 1:
+                tt = torch.tensor([steady_s], dtype=torch.float64, device='cuda')
+                dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+                steady_s = float(tt.item())
+            steady = {'steps': STEADY_STEPS, 'ms_per_step': round(steady_s / STEADY_STEPS * 1e3, 4),
+                      'value': round(wl['evals_per_step'] * STEADY_STEPS / steady_s, 1)}
+        leg = {'scaling': scaling, 'ms_per_step': round(elapsed / args.steps * 1e3, 4), 'steady': steady,
                'value': round(wl['evals_per_step'] * args.steps / elapsed, 1), 'unit': 'evals/s',
                'evals_per_step': wl['evals_per_step'], 'host_ms_per_step': round(host_ms, 4), 'finite': wl['finite'](),
                'exchange': exchange_name(), 'world_size_seen': (dist.get_world_size() if world > 1 else 1),
@@ -306,68 +324,70 @@ def main():
         return leg, wl, elapsed
 
     leg, wl, elapsed = timed_leg(args.scaling, True)
-    gpu_only = wl['gpu_only']() if ('gpu_only' in wl and world == 1) else None
-    device_noise = wl['device_noise']() if ('device_noise' in wl and world == 1) else None
     finite = leg['finite']
     ms_per_step = elapsed / args.steps * 1e3
     host_ms = leg['host_ms_per_step']
     evals_per_step, metric, dtype, describe, extra = wl['evals_per_step'], wl.get('metric'), wl['dtype'], wl['describe'], wl.get('extra', {})
     step_mode = leg['step_mode']
-    exchange = leg['exchange']
+    leg['all_reduce_us'] = None
 
-    pp = profile_pass(wl, L, 50)                         # (its own step count: --steps 20 would make the per-kernel averages noisy)
-    kernel_ms, kernel_sum, prof_ms = pp['kernel_ms'], pp['kernel_sum'], pp['ms_per_step']
-    roofline, kernel_rooflines, step_flops = rooflines(wl, pp)
+    # everything beside the headline: --full only, all of it after the timed steps
+    gpu_only = device_noise = pp = roofline = kernel_rooflines = step_flops = legs = gram = others = predictive = None
+    if args.full:
+        gpu_only = wl['gpu_only']() if ('gpu_only' in wl and world == 1) else None
+        device_noise = wl['device_noise']() if ('device_noise' in wl and world == 1) else None
 
-    def all_reduce_us(pp_):
-        """HIP-event time of the step's one exchange in the eager per-kernel pass (the in-graph collective cannot be timed from
-        outside the graph): RCCL's kernel on the compute stream, or torch.distributed's call"""
-        for key in ('allreduce_sum', 'allreduce_torch'):
-            if key in pp_['kernel_ms_raw']:
-                return round(pp_['kernel_ms_raw'][key] * 1e3, 2)
-        return None
-    leg['all_reduce_us'] = all_reduce_us(pp) if world > 1 else None
+        pp = profile_pass(wl, L, 50)                     # (its own step count: --steps 20 would make the per-kernel averages noisy)
+        roofline, kernel_rooflines, step_flops = rooflines(wl, pp)
 
-    # N > 1, headline configuration: BOTH scaling modes from the one invocation the driver makes -- weak (1024 tasks per GPU) and
-    # strong (1024 tasks in total: cfg #3 as BASELINE.json words it).  The line's own value / ms_per_step are the --scaling leg's.
-    legs = None
-    if world > 1 and args.config == 3:
-        legs = {args.scaling: leg}
-        other = 'strong' if args.scaling == 'weak' else 'weak'
-        del wl
-        torch.cuda.empty_cache()
-        leg2, wl2, _ = timed_leg(other, False)
-        leg2['all_reduce_us'] = all_reduce_us(profile_pass(wl2, L, 20))
-        legs[other] = leg2
-        # what the first real record needs to explain its own efficiency: a rank of the weak leg does the N = 1 job's work, so the
-        # strong leg's ideal step is that time / N; what is above it is the one-round-of-workgroups floor of a small shard plus the exchange
-        legs['strong']['ideal_ms_per_step'] = round(legs['weak']['ms_per_step'] / world, 4)
-        legs['strong']['ideal_source'] = 'legs.weak.ms_per_step (1024 tasks per GPU = the N = 1 job) / %d' % world
-        wl = wl2
+        def all_reduce_us(pp_):
+            """HIP-event time of the step's one exchange in the eager per-kernel pass (the in-graph collective cannot be timed from
+            outside the graph): RCCL's kernel on the compute stream, or torch.distributed's call"""
+            for key in ('allreduce_sum', 'allreduce_torch'):
+                if key in pp_['kernel_ms_raw']:
+                    return round(pp_['kernel_ms_raw'][key] * 1e3, 2)
+            return None
+        leg['all_reduce_us'] = all_reduce_us(pp) if world > 1 else None
 
-    gram = gram_leg(L) if (rank == 0 and args.config == 3) else None
+        # N > 1, headline configuration: BOTH scaling modes from one invocation -- weak (1024 tasks per GPU) and strong (1024 tasks
+        # in total: cfg #3 as BASELINE.json words it).  The line's own value / ms_per_step are the --scaling leg's.
+        if world > 1 and args.config == 3:
+            legs = {args.scaling: leg}
+            other = 'strong' if args.scaling == 'weak' else 'weak'
+            del wl
+            torch.cuda.empty_cache()
+            leg2, wl2, _ = timed_leg(other, False)
+            leg2['all_reduce_us'] = all_reduce_us(profile_pass(wl2, L, 20))
+            legs[other] = leg2
+            # what the first real record needs to explain its own efficiency: a rank of the weak leg does the N = 1 job's work, so the
+            # strong leg's ideal step is that time / N; what is above it is the one-round-of-workgroups floor of a small shard plus the
+            # exchange
+            legs['strong']['ideal_ms_per_step'] = round(legs['weak']['ms_per_step'] / world, 4)
+            legs['strong']['ideal_source'] = 'legs.weak.ms_per_step (1024 tasks per GPU = the N = 1 job) / %d' % world
+            wl = wl2
 
-    # the other BASELINE configurations (parity-test cases, not the headline): bounded legs on the same box so that their numbers
-    # are driver-visible too -- N = 1, default config only
-    others = predictive = None
-    if rank == 0 and world == 1 and args.config == 3 and not args.no_other_configs:
-        del wl
-        torch.cuda.empty_cache()
-        others = {}
-        for c in (1, 2, 4, 5, 'ref_svgd', 'ref_vi', 'ref_map', 'shard128'):
-            key = 'cfg%d' % c if isinstance(c, int) else c
+        gram = gram_leg(L) if (rank == 0 and args.config == 3) else None
+
+        # the other BASELINE configurations (parity-test cases, not the headline): bounded legs on the same box -- N = 1, default
+        # config only
+        if rank == 0 and world == 1 and args.config == 3 and not args.no_other_configs:
+            del wl
+            torch.cuda.empty_cache()
+            others = {}
+            for c in (1, 2, 4, 5, 'ref_svgd', 'ref_vi', 'ref_map', 'shard128'):
+                key = 'cfg%d' % c if isinstance(c, int) else c
+                try:
+                    others[key] = other_config_leg(c, M, L)
+                except Exception as exc:                 # (a side leg must never take the headline line down with it)
+                    others[key] = {'error': repr(exc)}
+                    torch.cuda.empty_cache()
             try:
-                others[key] = other_config_leg(c, M, L)
-            except Exception as exc:                     # (a side leg must never take the headline line down with it)
-                others[key] = {'error': repr(exc)}
-                torch.cuda.empty_cache()
-        try:
-            predictive = predictive_leg(L)
-        except Exception as exc:
-            predictive = {'error': repr(exc)}
+                predictive = predictive_leg(L)
+            except Exception as exc:
+                predictive = {'error': repr(exc)}
 
     if rank == 0:
-        cpu = None if (args.no_cpu_baseline or world > 1 or args.config != 3) else cpu_baseline()
+        cpu = None if (not args.full or args.no_cpu_baseline or world > 1 or args.config != 3) else cpu_baseline()
         value = evals_per_step * args.steps / elapsed
         out = assemble_line(
             metric='task-GP LML+grad evals/sec (n_ctx=64, d=4, 20 particles)' if args.config == 3 else metric, value=value,
@@ -381,7 +401,8 @@ def main():
             out['gpu_ms_per_step_noise_resident'] = gpu_only      # (PACOH-VI: the step without the host's noise draw, _vi_gpu_only)
         if device_noise is not None:
             out['ms_per_step_device_noise'] = device_noise        # (PACOH-VI with noise='device': wl_ref_vi)
-        out['predictive'] = predictive                    # (row A11 beside the LML: predictive_leg; None outside the default N = 1 run)
+        out['predictive'] = predictive                    # (row A11 beside the LML: predictive_leg; None outside the default N = 1 --full run)
+        out['full'] = args.full                           # (false: a plain run, the keys it does not measure are null)
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

@@ -166,15 +166,44 @@ def test_bench_dump_outputs_repeat(tmp_path):
     assert np.load(str(tmp_path / 'a' / 'particles.npy')).shape[0] == 20
 
 
-def test_bench_line_contract():
-    """`python bench.py` (child process) prints ONE JSON line with the driver's keys, BASELINE.json's metric, a live
-    roofline object and a bounded cpu_baseline; value is consistent with ms_per_step."""
+def test_bench_plain_line_is_the_headline_alone():
+    """`python bench.py` without --full (child process) prints ONE JSON line with the driver's keys, BASELINE.json's metric and a
+    value consistent with ms_per_step, and runs none of the side measurements: their keys are null"""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '2'], cwd=root,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
+                'vs_baseline', 'dtype', 'data', 'config', 'host_ms_per_step', 'step_mode'):
+        assert key in d, key
+    base = json.load(open(os.path.join(root, 'BASELINE.json')))
+    assert d['metric'].split(';')[0].strip() in base['metric'] and d['unit'] == 'evals/s'
+    assert d['n_gpus'] == 1 and d['steps'] == 3 and d['warmup'] == 2 and d['scaling'] == 'weak' and d['data'] == 'synthetic'
+    assert d['higher_is_better'] is True and d['vs_baseline'] is None and d['dtype'] == 'f32' and d['full'] is False
+    assert d['config']['finite'] is True and d['config']['evals_per_step'] == 1024 * 20
+    assert abs(d['value'] - d['config']['evals_per_step'] / (d['ms_per_step'] * 1e-3)) <= 1e-3 * d['value']
+    assert d['value'] >= 10000 and d['world_size_seen'] == 1 and d['host_ms_per_step'] < d['ms_per_step']
+    for key in ('steady', 'roofline', 'kernel_rooflines', 'gram_roofline', 'kernel_ms_per_step', 'kernel_sum_ms_per_step',
+                'profile_pass_ms_per_step', 'step_algorithmic_tflops', 'other_configs', 'predictive', 'cpu_baseline', 'legs'):
+        assert d[key] is None, key
+
+
+def test_bench_line_contract():
+    """`python bench.py --full` (child process) prints ONE JSON line with the driver's keys, BASELINE.json's metric, a live
+    roofline object and a bounded cpu_baseline; value is consistent with ms_per_step."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '2', '--full'], cwd=root,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

@@ -114,7 +114,7 @@ def test_two_ranks_on_one_gpu_match_single_process(kind):
 
 
 def test_bench_two_ranks_prints_both_scaling_legs():
-    """`torch.distributed.run --nproc-per-node 2 bench.py --gpus 2` (gloo transport: two ranks on the box's one GPU) prints ONE JSON
+    """`torch.distributed.run --nproc-per-node 2 bench.py --gpus 2 --full` (gloo transport: two ranks on the box's one GPU) prints ONE JSON
     line whose `legs` holds the weak and the strong scaling mode, each timed with the exchange in place"""
     import json
     import subprocess
@@ -122,7 +122,8 @@ def test_bench_two_ranks_prints_both_scaling_legs():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PACOH_BENCH_BACKEND='gloo')
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-                        '--master-port', str(_free_port()), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2'],
+                        '--master-port', str(_free_port()), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2',
+                        '--full'],
                        cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]

@@ -312,6 +312,30 @@ def test_bench_line_shape_with_both_scaling_legs():
     assert set(out['steady']) == {'steps', 'ms_per_step', 'value'} and out['steady']['steps'] == 200       # the steady-state region behind the timed one
 
 
+def test_bench_plain_line_shape():
+    """bench.py's JSON line of a plain run (no --full): no per-kernel pass, no side legs -- the headline keys as in a --full run, the
+    keys built on what it did not measure null"""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('pacoh_bench', os.path.join(root, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    leg = {'scaling': 'weak', 'ms_per_step': 0.41, 'steady': None, 'value': 20480 / 0.41e-3, 'unit': 'evals/s', 'evals_per_step': 20480,
+           'host_ms_per_step': 0.01, 'finite': True, 'exchange': None, 'world_size_seen': 1, 'step_mode': {'graph': True},
+           'tasks_total': 1024, 'all_reduce_us': None}
+    out = bench.assemble_line(metric='task-GP LML+grad evals/sec (n_ctx=64, d=4, 20 particles)', value=leg['value'], world=1, steps=20,
+                              warmup=5, ms_per_step=0.41, scaling='weak', dtype='f32', backend=None, world_size_seen=1, leg=leg, legs=None,
+                              host_ms=0.01, step_mode={'graph': True}, config={'workload': 'x'}, roofline=None, kernel_rooflines=None,
+                              step_flops=None, gram=None, pp=None, others=None, cpu=None)
+    json.loads(json.dumps(out))
+    assert out['value'] == round(leg['value'], 1) and out['ms_per_step'] == 0.41 and out['unit'] == 'evals/s'
+    assert out['higher_is_better'] is True and out['dtype'] == 'f32' and out['n_gpus'] == 1
+    for key in ('steady', 'roofline', 'kernel_rooflines', 'step_algorithmic_tflops', 'gram_roofline', 'kernel_ms_per_step',
+                'kernel_ms_per_step_events_raw', 'event_overhead_us', 'kernel_sum_ms_per_step', 'profile_pass_ms_per_step',
+                'launch_gaps_ms_per_step', 'other_configs', 'cpu_baseline', 'legs', 'all_reduce_us'):
+        assert out[key] is None, key
+
+
 def test_bench_dump_outputs_dtypes_and_size_cap(tmp_path):
     """bench.py --dump-outputs writes <name>.npy in float32 (float64 for fp64 arrays); an array above its share of the 64 MB budget
     is replaced by the same seeded sample of its elements on every call"""

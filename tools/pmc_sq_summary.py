@@ -21,7 +21,7 @@ def main(src, out):
                 c = acc.setdefault(name, {}).setdefault(row['Counter_Name'], [0.0, set()])
                 c[0] += float(row['Counter_Value'])
                 c[1].add((path, row['Dispatch_Id']))
-    lines = ['rocprofv3 --kernel-trace --pmc <counters> -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline (one pass per counter group);',
+    lines = ['rocprofv3 --kernel-trace --pmc <counters> -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline (one pass per counter group);',
              'per-dispatch averages, summed over the XCDs/SEs as rocprofv3 reports them', '']
     for name in sorted(acc, key=lambda k: -acc[k].get('SQ_WAVE_CYCLES', [0.0, {0}])[0] / max(1, len(acc[k].get('SQ_WAVE_CYCLES', [0, {0}])[1]))):
         d = {k: v[0] / max(1, len(v[1])) for k, v in acc[name].items()}

@@ -36,7 +36,7 @@ def main(src, out, passes=0):
         for name, d in acc.items():
             if 'FETCH_SIZE' in d or 'WRITE_SIZE' in d:
                 per_pass[name] = int((2 * d.get('FETCH_SIZE', [0.0])[0] + d.get('WRITE_SIZE', [0.0])[0]) * 1024 / passes)
-    note = ('rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, kernel-trace only) of `bench.py --steps 3 --warmup 1 '
+    note = ('rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, kernel-trace only) of `bench.py --full --steps 3 --warmup 1 '
             '--no-cpu-baseline`, averaged per launch; raw counters are in KB. hbm_bytes applies the gfx950 correction of '
             'MI355X_MICROARCH.md (FETCH_SIZE reports half of a wide coalesced read stream): hbm_bytes = (2*FETCH_SIZE + WRITE_SIZE) * 1024.')
     # the kernel sources this profile was taken on (bench.py marks its `traffic` figures stale when they have changed since)
