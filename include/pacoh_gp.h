@@ -144,6 +144,27 @@ int pacoh_gp_predict(const void* z_ctx, int z_div, const void* mean_ctx, int mea
                      const int32_t* n_valid, void* mu, void* var, void* cov, int32_t* info,
                      void* workspace, int B, int P, int n, int m, int f, int dtype, void* stream);
 
+/* ---- leave-one-out predictive and LOO log pseudo-likelihood, small n --------------------------------
+ * With K = os*k(Z,Z) + noise*I = L L^T, alpha = K^-1 (y - mean), d_i = [K^-1]_ii (Rasmussen & Williams 5.4.2):
+ *   mu_loo[b,i]  = y_i - alpha_i / d_i      -- the posterior mean at z_i of the GP conditioned on the OTHER n_b - 1 points
+ *   var_loo[b,i] = 1 / d_i                  -- its predictive variance, observation noise included (like pacoh_gp_predict's var)
+ *   lpd[b]       = (1/n_b) sum_i log N(y_i; mu_loo[b,i], var_loo[b,i])
+ * without a refit.  Upstream counterpart: gpytorch.mlls.LeaveOneOutPseudoLikelihood (the reference itself has no LOO path; it
+ * sits on gpytorch).  One fused launch (csrc/gp_loo.hip): Gram build, Cholesky with the jitter ladder, L^-1 in place in LDS, d and
+ * alpha from its columns; neither K nor L is written to HBM.  Arguments, problem order b = t*P + p, z_div / y_div sharing, mean
+ * modes, kernel family in `f`, outputscale NULL = 1, info[] values and normalised space exactly as pacoh_gp_lml_fwd.
+ * Jitter: when rung k >= 1 was needed (info[b] = k) every output is that of the JITTERED matrix K + j I; info[b] = -1: mu_loo[b,:],
+ * var_loo[b,:] and lpd[b] are NaN.  Ragged tasks, nv = clamp(n_valid[b / y_div], 0, n): entries i >= nv of mu_loo / var_loo are
+ * written as 0, lpd[b] averages over the nv points; nv = 0: lpd = 0, info = 0; nv = 1: the prior predictive mean_1, K_11.
+ * Any of mu_loo[B,n], var_loo[B,n], lpd[B], info[B] may be NULL (skipped), but not all of the first three (PACOH_EINVAL).
+ * Limits: n <= pacoh_gp_loo_max_n(dtype) (>= 128, and >= pacoh_gp_small_max_n(dtype, 1)), else PACOH_ELIMIT: there is NO
+ * large-context (HBM-resident) LOO path.  No gradients. */
+int pacoh_gp_loo_max_n(int dtype);
+int pacoh_gp_loo(const void* z, int z_div, const void* mean, int mean_mode, const void* y, int y_div,
+                 const void* lengthscale, const void* outputscale, const void* noise, const int32_t* n_valid,
+                 void* mu_loo, void* var_loo, void* lpd, int32_t* info,
+                 int B, int P, int n, int f, int dtype, void* stream);
+
 /* ---- dense path (large n): Cholesky-based Gaussian log-density of materialised covariances -----
  * logp[b] = log N(resid[b]; 0, A[b]) * scale,  A[B,n,n] symmetric (lower triangle read), destroyed
  * (overwritten by its Cholesky factor).  With A from pacoh_gram_rbf_ard(..., add_noise_diag=1) and

@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .abstract import _calib_error
+from .abstract import _calib_error, _loo_metrics, _raise_not_psd
 from .config import get_device
 from .distributions import GaussianPredictive
 from .engine import GPEngine, NotPSDError, ParamLayout, TaskBatch
@@ -174,6 +174,23 @@ class GPRegressionLearned:
         avg_ll = pred.log_prob(ty) / ty.shape[0]
         rmse = torch.mean(torch.pow(pred.mean - ty, 2)).sqrt()
         return avg_ll.cpu().item(), rmse.cpu().item(), _calib_error(pred, ty).cpu().item()
+
+    def loo(self, return_density=False):
+        """leave-one-out predictive on the training set itself: entry i is the predictive at train_x[i] of the GP conditioned on
+        the other n - 1 training points -> (mean[n], std[n]) numpy, or the distribution (no joint covariance: .log_prob raises,
+        .marginal_log_prob / .cdf / .icdf work).  No refit; training sets beyond L.gp_loo_max_n points are refused."""
+        n = self.n_train_samples
+        mu, var, _, info = self.engine.loo_tasks(self.theta, self._ctx_x[:n].unsqueeze(0), self._ctx_y[:n].reshape(1, -1))
+        _raise_not_psd(info)
+        dist = GaussianPredictive(mu, var, None, self.y_mean.reshape(-1)[0], self.y_std.reshape(-1)[0], mixture=False)
+        if return_density:
+            return dist
+        return dist.mean.cpu().numpy(), dist.stddev.cpu().numpy()
+
+    def eval_loo(self):
+        """-> (avg LOO log-likelihood per training point, rmse, calibration error), each training point predicted from the others"""
+        ty = self._ctx_y[:self.n_train_samples] * float(self.y_std.reshape(-1)[0]) + float(self.y_mean.reshape(-1)[0])
+        return _loo_metrics(self.loo(return_density=True), ty)
 
     def confidence_intervals(self, test_x, confidence=0.9, **kwargs):
         """abstract.py:50-57 -> (ucb, lcb)"""

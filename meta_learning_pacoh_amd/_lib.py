@@ -36,6 +36,8 @@ SIGNATURES = {
     'pacoh_gram_rbf_ard': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'pacoh_gp_small_max_n': (_i, [_i, _i]),
     'pacoh_gp_lml_fwd': (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'pacoh_gp_loo_max_n': (_i, [_i]),
+    'pacoh_gp_loo': (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'pacoh_gp_lml_fwdbwd': (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                  _i, _i, _i, _i, _i, _vp]),
     'pacoh_gp_predict_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
@@ -330,6 +332,52 @@ def gp_lml_fwd(z, z_div, mean, mean_mode, y, y_div, lengthscale, outputscale, no
                                     _ptr(outputscale, z), _ptr(noise, z), _ptr(n_valid), _ptr(lml), _ptr(alpha), _ptr(L),
                                     _ptr(info), B, P, n, _kf(f, kernel), dtype_code(z), _stream()), 'pacoh_gp_lml_fwd')
     return lml, alpha, L, info
+
+
+def gp_loo_max_n(dtype):
+    """largest context size of gp_loo (one LDS-resident matrix per problem; there is no large-context LOO path)"""
+    return load_library().pacoh_gp_loo_max_n(F32 if dtype == torch.float32 else F64)
+
+
+def gp_loo(z, z_div, mean, mean_mode, y, y_div, lengthscale, outputscale, noise, B, P, n_valid=None, kernel=KERNEL_RBF):
+    """leave-one-out predictive of B = T*P GP problems in one launch (normalised space, observation noise included):
+    -> mu_loo [B,n], var_loo [B,n], lpd [B] (mean LOO log-density over the task's valid points), info [B].
+    Arguments as gp_lml_fwd: z [B / z_div, n, f], y [B / y_div, n], mean None | [B,n] | [P], lengthscale [P,f], outputscale [P] | None,
+    noise [P], n_valid int32 [B / y_div] | None.  A jitter rung (info 1..3) means the quantities of the jittered matrix; info < 0: NaN."""
+    lib = load_library()
+    if z.dim() != 3 or z.shape[0] * z_div < B:
+        raise ValueError('z must be [>= %d,n,f] for z_div %d, got %s' % (-(-B // max(1, z_div)), z_div, tuple(z.shape)))
+    n, f = z.shape[-2], z.shape[-1]
+    dev, dt = z.device, z.dtype
+    if y.dim() != 2 or y.shape[1] != n or y.shape[0] * y_div < B:
+        raise ValueError('y must be [>= %d,%d] for y_div %d, got %s' % (-(-B // max(1, y_div)), n, y_div, tuple(y.shape)))
+    if B <= 0 or P <= 0 or B % P:
+        raise ValueError('B must be a positive multiple of P, got B = %d, P = %d' % (B, P))
+    if tuple(lengthscale.shape) != (P, f) or noise.numel() != P or (outputscale is not None and outputscale.numel() != P):
+        raise ValueError('lengthscale must be [%d,%d], noise and outputscale [%d]' % (P, f, P))
+    if mean_mode == MEAN_VECTOR:
+        if mean is None or mean.numel() != B * n:
+            raise ValueError('mean must be [%d,%d] for MEAN_VECTOR' % (B, n))
+    elif mean_mode == MEAN_CONST:
+        if mean is None or mean.numel() != P:
+            raise ValueError('mean must be [%d] for MEAN_CONST' % P)
+    elif mean_mode != MEAN_ZERO:
+        raise ValueError('unknown mean_mode %r' % (mean_mode,))
+    if n_valid is not None and (n_valid.dtype != torch.int32 or n_valid.numel() * y_div < B):
+        raise ValueError('n_valid must be int32 with >= %d entries, got %s %s' % (-(-B // y_div), n_valid.dtype, tuple(n_valid.shape)))
+    limit = gp_loo_max_n(dt)
+    if n > limit:
+        raise RuntimeError('leave-one-out needs the context in LDS: n = %d is beyond the limit of %d points for %s '
+                           '(there is no large-context LOO path)' % (n, limit, dt))
+    mu = torch.empty(B, n, dtype=dt, device=dev)
+    var = torch.empty(B, n, dtype=dt, device=dev)
+    lpd = torch.empty(B, dtype=dt, device=dev)
+    info = torch.empty(B, dtype=torch.int32, device=dev)
+    with _Timed('gp_loo'):
+        _check(lib.pacoh_gp_loo(_ptr(z), z_div, _ptr(mean, z), mean_mode, _ptr(y, z), y_div, _ptr(lengthscale, z), _ptr(outputscale, z),
+                                _ptr(noise, z), _ptr(n_valid), _ptr(mu), _ptr(var), _ptr(lpd), _ptr(info), B, P, n, _kf(f, kernel),
+                                dtype_code(z), _stream()), 'pacoh_gp_loo')
+    return mu, var, lpd, info
 
 
 _DENSE_WS = {}

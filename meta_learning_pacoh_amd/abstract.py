@@ -8,6 +8,7 @@ import torch
 from . import _lib as L
 from .config import get_device
 from .distributions import GaussianPredictive
+from .engine import NotPSDError
 from .util import _handle_input_dimensionality, get_logger
 
 
@@ -106,6 +107,76 @@ class RegressionModelMetaLearned:
         calib = L.calib_error(L.mixture_cdf(mu3, var3, ty, y_mean, y_std))
         return torch.stack([ll / m, rmse, calib], dim=1).double().cpu().numpy()
 
+    # -- leave-one-out cross-validation on the context itself (Rasmussen & Williams 5.4.2; no refit, one fused launch) -------------
+    def _loo_params(self, T, **kwargs):
+        """the parameter rows predict(**kwargs) conditions on, for T tasks -> (theta, mixture, per_task)"""
+        params = self._eval_params(**kwargs)
+        if params is None:
+            raise TypeError('loo: predict() of %s takes no arguments %s' % (type(self).__name__, sorted(kwargs)))
+        theta, mixture, per_task = params
+        return (theta(T) if per_task else theta), mixture, per_task
+
+    def loo(self, context_x, context_y, return_density=False, **kwargs):
+        """leave-one-out predictive on the context points: entry i is the predictive at context_x[i] of the model conditioned on
+        the OTHER n - 1 points (observation noise included), on the parameter rows predict(**kwargs) conditions on (MAP: the
+        row; SVGD: the particles as a mixture; VI: mode / n_posterior_samples) -> (mean[n], std[n]) numpy, or the
+        GaussianPredictive over the n context points.  That object has no joint covariance: .mean / .stddev / .cdf / .icdf /
+        .marginal_log_prob work, .log_prob raises.  Contexts beyond L.gp_loo_max_n points are refused."""
+        cx, cy = self._prepare_data_per_task(context_x, context_y)
+        theta, mixture, per_task = self._loo_params(1, **kwargs)
+        mu, var, _, info = self.engine.loo_tasks(theta, self._to_device(cx).unsqueeze(0), self._to_device(cy).reshape(1, -1),
+                                                 theta_per_task=per_task)
+        _raise_not_psd(info)
+        dist = GaussianPredictive(mu, var, None, self.y_mean.reshape(-1)[0], self.y_std.reshape(-1)[0], mixture=mixture)
+        if return_density:
+            return dist
+        return dist.mean.cpu().numpy(), dist.stddev.cpu().numpy()
+
+    def eval_loo(self, context_x, context_y, **kwargs):
+        """eval() on the context itself, each point predicted from the others -> (avg LOO log-likelihood per point, rmse,
+        calibration error); the per-point marginal density stands where eval() has the joint one"""
+        _, context_y = _handle_input_dimensionality(context_x, context_y)
+        y = torch.from_numpy(context_y).float().flatten().to(self.device)
+        dist = self.loo(context_x, context_y, return_density=True, **kwargs)
+        return _loo_metrics(dist, y)
+
+    def eval_loo_datasets(self, tuples, **kwargs):
+        """mean over the tasks (x, y) of eval_loo()'s three metrics.  Tasks of equal size go through ONE leave-one-out pass over
+        T*P problems whenever _eval_params supplies the parameter rows (as eval_datasets; VI draws its rows per task in task order);
+        otherwise a loop over eval_loo()"""
+        assert (all([len(t) == 2 for t in tuples]))
+        if self._eval_params(**kwargs) is None:
+            ll, rmse, calib = list(zip(*[self.eval_loo(x, y, **kwargs) for x, y in tuples]))
+            return np.mean(ll), np.mean(rmse), np.mean(calib)
+        theta, mixture, per_task = self._loo_params(len(tuples), **kwargs)
+        tuples = [_handle_input_dimensionality(x, y) for x, y in tuples]
+        groups = {}
+        for i, (x, _) in enumerate(tuples):
+            groups.setdefault(x.shape[0], []).append(i)
+        P = theta.shape[0] // len(tuples) if per_task else theta.shape[0]
+        if per_task:
+            theta = theta.view(len(tuples), P, -1)
+        y_mean, y_std = float(self.y_mean.reshape(-1)[0]), float(self.y_std.reshape(-1)[0])
+        metrics = np.empty((len(tuples), 3), dtype=np.float64)
+        for n, ids in groups.items():
+            T = len(ids)
+            ctx = [self._prepare_data_per_task(*tuples[i]) for i in ids]
+            cx = self._to_device(np.stack([c[0] for c in ctx]))
+            cy = self._to_device(np.stack([c[1] for c in ctx]))
+            ty = torch.from_numpy(np.stack([tuples[i][1].flatten() for i in ids])).float().to(self.dtype).to(self.device)     # [T,n]
+            rows = theta[ids].reshape(T * P, -1).contiguous() if per_task else theta
+            mu, var, _, info = self.engine.loo_tasks(rows, cx, cy, theta_per_task=per_task)
+            _raise_not_psd(info)
+            mu3, var3 = mu.view(T, P, n), var.view(T, P, n)
+            z = ((ty - y_mean) / y_std).unsqueeze(1) - mu3
+            logp = -0.5 * (z * z / var3 + torch.log(var3) + math.log(2.0 * math.pi)) - math.log(y_std)
+            ll = torch.logsumexp(logp, dim=1) - math.log(P) if mixture else logp[:, 0]
+            mean = (mu3 * y_std + y_mean).mean(1) if mixture else mu3[:, 0] * y_std + y_mean
+            rmse = torch.mean(torch.pow(mean - ty, 2), dim=1).sqrt()
+            calib = L.calib_error(L.mixture_cdf(mu3, var3, ty, y_mean, y_std))
+            metrics[ids] = torch.stack([ll.mean(1), rmse, calib], dim=1).double().cpu().numpy()
+        return np.mean(metrics[:, 0]), np.mean(metrics[:, 1]), np.mean(metrics[:, 2])
+
     def confidence_intervals(self, context_x, context_y, test_x, confidence=0.9, **kwargs):
         """abstract.py:183-204 -> (ucb, lcb)"""
         pred_dist = self.predict(context_x, context_y, test_x, return_density=True, **kwargs)
@@ -174,3 +245,18 @@ class RegressionModelMetaLearned:
 def _calib_error(pred_dist, test_t_tensor):
     """abstract.py:260-272 on the vectorised (marginal) predictive"""
     return L.calib_error(pred_dist.cdf(test_t_tensor))
+
+
+def _loo_metrics(dist, y):
+    """(avg LOO log-likelihood per point, rmse, calibration error) of a leave-one-out predictive against the targets it left out"""
+    avg_ll = torch.mean(dist.marginal_log_prob(y))
+    rmse = torch.mean(torch.pow(dist.mean - y, 2)).sqrt()
+    return avg_ll.cpu().item(), rmse.cpu().item(), _calib_error(dist, y).cpu().item()
+
+
+def _raise_not_psd(info):
+    """a failed problem (info < 0) raises what sampling raises (one host sync)"""
+    bad = torch.nonzero(info < 0).flatten().tolist()
+    if bad:
+        raise NotPSDError('the kernel matrix of problem %s was not positive definite even after adding jitter'
+                          % ', '.join(str(b) for b in bad))

@@ -2,7 +2,8 @@
 
 They play the role of AffineTransformedDistribution(MultivariateNormal) (meta_learn/models.py:15-43) and
 EqualWeightedMixtureDist(batched=True) (models.py:74-140) in the reference: .mean, .stddev, .variance,
-.log_prob (JOINT Gaussian log-density over all test points, per component), .cdf / .icdf (marginals), and joint draws
+.log_prob (JOINT Gaussian log-density over all test points, per component), .cdf / .icdf (marginals), .marginal_log_prob (per-point
+log-density of the marginals: what the leave-one-out predictive, which has no joint covariance, is scored with), and joint draws
 .sample / .rsample (MultivariateNormal.rsample of the reference's single-Gaussian predictive).
 The joint log-density runs the dense HIP Cholesky kernel on the predictive covariance; the draws factor it once per object
 (pacoh_mvn_factor) and transform the standard normals on the matrix cores (pacoh_mvn_sample)."""
@@ -65,6 +66,17 @@ class GaussianPredictive:
         if not self.mixture:
             return logp[0]
         return torch.logsumexp(logp, dim=0, keepdim=True) - math.log(self.num_dists)
+
+    def marginal_log_prob(self, value):
+        """per-point log-density [m] of the targets under the MARGINAL predictive of each point (original units); mixture:
+        logsumexp over the components - log P.  Needs no covariance; elementwise torch, so it also works on CPU tensors"""
+        value = torch.as_tensor(value, dtype=self._mu_n.dtype, device=self._mu_n.device).flatten()
+        var = self._var_n
+        z = ((value - self.y_mean) / self.y_std).unsqueeze(0) - self._mu_n                  # [P,m]
+        logp = -0.5 * (z * z / var + torch.log(var) + math.log(2.0 * math.pi)) - math.log(self.y_std)
+        if not self.mixture:
+            return logp[0]
+        return torch.logsumexp(logp, dim=0) - math.log(self.num_dists)
 
     def cdf(self, value):
         """marginal cdf per test point (mixture: mean over components, models.py:124-131)"""

@@ -810,3 +810,16 @@ class GPEngine:
         zt, zt_div, mt, _ = self._features(theta, tst_x.contiguous(), T, m, theta_per_task)
         return L.gp_predict(zc, zc_div, mc, mode, ctx_y.contiguous(), P, zt, zt_div, mt, ls, os_, noise, T * P, rows, want_cov=want_cov,
                             kernel=self.layout.kernel_code)
+
+    def loo_tasks(self, theta, ctx_x, ctx_y, n_valid=None, theta_per_task=False):
+        """leave-one-out predictive of T tasks of equal shape for every parameter row, without a refit: ctx_x[T,n,d], ctx_y[T,n],
+        n_valid int32 [T] | None -> mu[T*P,n], var[T*P,n] (the GP conditioned on the task's other points, evaluated at point i;
+        normalised space, observation noise included), lpd[T*P] (mean LOO log-density over the task's points), info[T*P];
+        problem b = t*P + p.  theta_per_task as predict_tasks.  One fused launch (L.gp_loo); n <= L.gp_loo_max_n(dtype)."""
+        rows = theta.shape[0]
+        T, n = ctx_x.shape[0], ctx_x.shape[1]
+        P = rows // T if theta_per_task else rows
+        ls, os_, noise = self._hypers(theta)
+        z, z_div, mean, mode = self._features(theta, ctx_x.contiguous(), T, n, theta_per_task)
+        return L.gp_loo(z, z_div, mean, mode, ctx_y.contiguous(), P, ls, os_, noise, T * P, rows, n_valid=n_valid,
+                        kernel=self.layout.kernel_code)
