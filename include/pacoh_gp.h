@@ -465,6 +465,74 @@ int pacoh_svgd_update_next(void* X, const void* score, const void* prior_mean, c
                            int off_ls, int f, int off_os, int off_noise, double noise_floor, void* ls, void* os, void* noise,
                            int bandwidth_ready, int dtype, void* stream);
 
+/* Distinct tasks of a step's draw.  A step's tb tasks are drawn WITH replacement (GPR_meta_svgd.py:102): a draw of 1024 from 1024
+ * tasks holds ~647 distinct ones, and every repeated draw recomputes the same numbers.  The host rewrites each row of idx_all as the
+ * row's distinct task ids in order of first occurrence (padded to tb with any valid id), with nact_all[row] = how many they are and
+ * mult_all[row, tb] = how often each was drawn (`dtype` values, 0 for the padding):  sum_{draws t} g(t, p) = sum_{distinct u}
+ * mult[u] g(u, p).  The launch that gathers a row's tasks also copies its nact / mult entries into the fixed buffers n_act[1] /
+ * task_w[tb] (pacoh_active_feed; the protocol of the batch buffers), and the step's kernels read them there (pacoh_active_tasks):
+ *   pacoh_mlp2_fwd[_svgd]_active  the two networks run on the first *n_act tasks' rows only; the tiles are re-split over the launch's
+ *                                 workgroups on the device (the grid is that of tb tasks: a captured graph fixes it);
+ *   pacoh_gp_lml_fwdbwd_active    problems of tasks >= *n_act return at once (their outputs are left as they are), the upstream
+ *                                 gradient of problem b is g_lml[b] * task_w[b / P];
+ *   pacoh_mlp2_bwd_hyper_active   the backward as the forward; the hyper-parameter sums run over the first *n_act tasks (the GP call
+ *                                 has weighted their terms), lik[p] = lik_scale * sum_t task_w[t] lml[t, p].
+ * fp32, the fused networks (pacoh_mlp_fused_path) and the register-resident GP kernel (n <= 128, f <= 4, RBF) only: PACOH_ELIMIT
+ * elsewhere.  A row without repeated draws is the row itself, all weights 1 and *n_act == tb: the very same bits as the plain calls.
+ * act / feed == NULL: the plain call. */
+typedef struct pacoh_active_tasks {
+    const int32_t* n_act;                  /* device, 1 value: the leading tasks of the step's batch that are evaluated */
+    const void* task_w;                    /* device, tb values: their multiplicities */
+} pacoh_active_tasks;
+typedef struct pacoh_active_feed {
+    const int32_t* nact_all;               /* device, one per row of idx_all */
+    const void* mult_all;                  /* device, [rows, tb] */
+    int32_t* n_act; void* task_w;          /* the fixed buffers (pacoh_active_tasks) the gathered row's values go to */
+} pacoh_active_feed;
+int pacoh_mlp2_fwd_active(const pacoh_active_tasks* act, const void* x, int x_div, const void* theta, long theta_stride, int P, int d_in,
+                          const int32_t* hidden, int n_hidden, long off_a, int d_out_a, void* out_a, long off_b, int d_out_b,
+                          void* out_b, void* workspace, void* stash, int B, int n, int dtype, void* stream);
+int pacoh_mlp2_fwd_svgd_active(const pacoh_active_tasks* act, const void* x, int x_div, const void* theta, long theta_stride, int P,
+                               int d_in, const int32_t* hidden, int n_hidden, long off_a, int d_out_a, void* out_a, long off_b,
+                               int d_out_b, void* out_b, void* workspace, void* stash, int B, int n,
+                               const void* svgd_X, void* svgd_workspace, int svgd_P, int svgd_D, int64_t* counter,
+                               int dtype, void* stream);
+int pacoh_gp_lml_fwdbwd_active(const pacoh_active_tasks* act, const void* z, int z_div, const void* mean, int mean_mode,
+                               const void* y, int y_div, const void* lengthscale, const void* outputscale,
+                               const void* noise, const int32_t* n_valid, const void* g_lml,
+                               void* lml, void* d_z, void* d_mean, void* d_lengthscale,
+                               void* d_outputscale, void* d_noise, int32_t* info,
+                               int B, int P, int n, int f, int dtype, void* stream);
+int pacoh_mlp2_bwd_hyper_active(const pacoh_active_tasks* act, const void* x, int x_div, const void* theta, long theta_stride, int P,
+                                int d_in, const int32_t* hidden, int n_hidden, long off_a, int d_out_a, const void* g_a, long off_b,
+                                int d_out_b, const void* g_b, void* d_theta, long d_theta_stride, int accumulate,
+                                void* workspace, const void* stash, int B, int n,
+                                int T, int off_ls, int f, int off_os, int off_noise, int off_const, const void* d_lengthscale,
+                                const void* d_outputscale, const void* d_noise, const void* d_const, const void* lml, void* lik,
+                                double lik_scale, const int32_t* info, int32_t* fail_flag, void* svgd_workspace, int svgd_P, int svgd_D,
+                                const pacoh_adam_inline* opt, int dtype, void* stream);
+int pacoh_step_begin_active(const pacoh_active_feed* feed, const int64_t* idx_all, int tb, const void* sc_all, int n_sc,
+                            const void* aux_all, long n_aux, int64_t* counter, int32_t* ticket, void* sc_out, void* aux_out,
+                            const void* x, const void* y, const int32_t* n_valid, void* out_x, void* out_y, int32_t* out_n_valid, int n, int d,
+                            const void* theta, long theta_stride, int P, int off_ls, int f, int off_os, int off_noise, double noise_floor,
+                            void* ls, void* os, void* noise, int advance, const void* svgd_X, void* svgd_workspace, int svgd_P, int svgd_D,
+                            int dtype, void* stream);
+int pacoh_svgd_update_next_active(const pacoh_active_feed* feed, void* X, const void* score, const void* prior_mean, const void* prior_std,
+                                  double prior_factor, double bandwidth, int use_adam, double beta1, double beta2, void* exp_avg,
+                                  void* exp_avg_sq, void* bw_out, void* workspace, int P, int D,
+                                  const int64_t* counter, void* sc2, int n_sc, const int64_t* idx_all, int tb, const void* sc_all,
+                                  const void* x, const void* y, const int32_t* n_valid, void* out_x, void* out_y,
+                                  int32_t* out_n_valid, int n, int d,
+                                  int off_ls, int f, int off_os, int off_noise, double noise_floor, void* ls, void* os, void* noise,
+                                  int bandwidth_ready, int dtype, void* stream);
+/* The device-side re-split of the fused networks' tile range (csrc/mlp_fused_split.h), for tests: tiles per workgroup when tiles_eff
+ * of the tiles_full tiles the launch was planned for (wgs workgroups of tpw_host tiles each) are live. */
+int pacoh_mlp_fused_split(int tiles_eff, int tiles_full, int wgs, int tpw_host);
+/* The host plan of the fused forward (bwd = 0) / backward (bwd != 0) launch for R rows per parameter row, P parameter rows, `nets`
+ * networks of n_hidden hidden layers and `resident` resident workgroups (backward; <= 0: ask the device): tile points, workgroups per
+ * (parameter row, network), tiles per workgroup. */
+int pacoh_mlp_fused_plan(int R, int P, int nets, int n_hidden, int bwd, int resident, int* tile_points, int* wgs, int* tiles_per_wg);
+
 /* Same update direction with the IMQ particle kernel k_ij = (alpha + sum_d (X_jd - X_id)^2 / h_d)^beta
  * (alpha > 0, beta < 0).  bandwidth > 0: h_d = bandwidth for every d.  bandwidth <= 0: per-dimension median
  * heuristic h_d = lower-median_{a<b} (X_bd - X_ad)^2 / ln(P+1) (torch.median semantics), written to h_out[D]

@@ -123,6 +123,30 @@ class _RandomGPLearner(StepDriver, RegressionModelMetaLearned):
             self._task_plan, self._task_ws = plan, ws
         return ws
 
+    # Duplicate draws (the tasks of a step are drawn WITH replacement: _take_idx).  A draw of 1024 from 1024 tasks holds ~647 distinct
+    # ones; the networks, the GP and their backward of a repeated draw recompute the same numbers on the same inputs.  The feed then
+    # hands the kernels each draw's distinct tasks with their multiplicities (engine.distinct_rows; include/pacoh_gp.h,
+    # pacoh_active_tasks): sum_{draws t} g(t, p) = sum_{distinct u} count_u g(u, p).  The pre-factor keeps using the draw itself.
+    DEDUP_MIN_PROBLEMS = 4096    # one resident round of the GP kernel (4 waves x 4 SIMDs x 256 CUs): below it the three large kernels
+                                 # are a single round of workgroups, and fewer problems do not shorten a launch
+
+    def _setup_dedup(self, rows, tb_local):
+        """switch the step feed to distinct tasks where the step runs on the kernels that take them -- fp32, both networks on the
+        fused kernels, the GP on the register-resident kernel (RBF features, n <= 128, f <= 4), not the task-fused small-grid step --
+        and has at least DEDUP_MIN_PROBLEMS (task, parameter row) problems.  PACOH_SVGD_DEDUP=0 / 1: never / wherever eligible
+        (tests, A/B).  The same for every launch sequence of the step (pipelined or not, replayed or eager)."""
+        force = os.environ.get('PACOH_SVGD_DEDUP')
+        lay = self.layout
+        if force == '0' or tb_local < 1 or self.dtype != torch.float32 or self._task_ws is not None or L.FORCE_DENSE:
+            return
+        if self.engine._paired_nets() is None or lay.kernel_code != L.KERNEL_RBF or self.tasks.n > 128 or lay.feature_dim > 4:
+            return
+        if not all(L.mlp_fused_path(tb_local * rows, rows, self.tasks.n, lay.input_dim, list(lay.mean_nn_layers), d_out, self.dtype)
+                   for d_out in (1, lay.feature_dim)):
+            return
+        if force == '1' or tb_local * rows >= self.DEDUP_MIN_PROBLEMS:
+            self._feed.enable_dedup()
+
     def _idx_uploader(self):
         up = getattr(self, '_idx_up', None)
         if up is None:
@@ -200,6 +224,7 @@ class GPRegressionMetaLearnedSVGD(_RandomGPLearner):
             self._imq_h = torch.empty(D, dtype=self.dtype, device=self.device) if self.bandwidth is None else None
             self._imq_ws = L.svgd_imq_workspace(self.particles)
         self._setup_task_fused(P, tb_local)
+        self._setup_dedup(P, tb_local)
         if self._pipelined:
             self._feed.pipeline(self.tasks, self.engine, self.particles)
         # median bandwidth computed beside the hyper-parameter reduction instead of inside the update (P <= 64: one wavefront's sort)
@@ -214,7 +239,8 @@ class GPRegressionMetaLearnedSVGD(_RandomGPLearner):
         if self._pipelined:
             self.engine.lml_and_grad(self.particles, self._feed.batch, weight=1.0, lik_out=self._lik, lik_scale=1.0,
                                      grad_out=self._score, fail_flag=self._fail, hypers=self._feed.hyp,
-                                     svgd_tail=(self.particles, self._svgd_ws, self._feed.ctr, self._bw_ahead))
+                                     svgd_tail=(self.particles, self._svgd_ws, self._feed.ctr, self._bw_ahead),
+                                     active=self._feed.active())
             return
         # select + gather + hyper transforms + the particles' distance matrix: one launch; the counter is advanced by the update
         # (IMQ: no distance matrix -- its bandwidths are per-dimension medians; the counter is advanced by the Adam launch, or
@@ -230,7 +256,7 @@ class GPRegressionMetaLearnedSVGD(_RandomGPLearner):
             L.svgd_task_step(self._task_plan, self.particles, batch, hyp, self._score, self._lik, 1.0, self._fail, self._task_ws)
             return
         self.engine.lml_and_grad(self.particles, batch, weight=1.0, lik_out=self._lik, lik_scale=1.0, grad_out=self._score,
-                                 fail_flag=self._fail, hypers=hyp)
+                                 fail_flag=self._fail, hypers=hyp, active=self._feed.active())
 
     def _body_update(self):
         """prior score + pre-factor + bandwidth + phi + optimizer in one launch (distances: _body_likelihood), particles updated

@@ -123,7 +123,14 @@ SIGNATURES = {
     'pacoh_comm_init': (_i, [_vp, _i, _i, _c.POINTER(_vp)]),
     'pacoh_allreduce_sum': (_i, [_vp, _l, _i, _vp, _vp]),
     'pacoh_comm_destroy': (_i, [_vp]),
+    'pacoh_mlp_fused_split': (_i, [_i, _i, _i, _i]),
+    'pacoh_mlp_fused_plan': (_i, [_i, _i, _i, _i, _i, _i, _ip, _ip, _ip]),
 }
+# the calls of a distinct-task SVGD step (include/pacoh_gp.h, pacoh_active_tasks / pacoh_active_feed): the plain call's arguments behind
+# a pointer to the struct
+for _name in ('pacoh_mlp2_fwd', 'pacoh_mlp2_fwd_svgd', 'pacoh_gp_lml_fwdbwd', 'pacoh_mlp2_bwd_hyper', 'pacoh_step_begin',
+              'pacoh_svgd_update_next'):
+    SIGNATURES[_name + '_active'] = (_i, [_vp] + SIGNATURES[_name][1])
 
 _lib = None
 ABI_VERSION = 14              # pacoh_abi_version() of the library this table was written for
@@ -148,6 +155,39 @@ def load_library():
                                % (LIB_PATH, lib.pacoh_abi_version(), ABI_VERSION))
         _lib = lib
     return _lib
+
+
+class ActiveTasks(ctypes.Structure):
+    """pacoh_active_tasks: the step's count of distinct tasks (int32 [1]) and their multiplicities ([tb]), both in device memory"""
+    _fields_ = [('n_act', _vp), ('task_w', _vp)]
+
+
+class ActiveFeed(ctypes.Structure):
+    """pacoh_active_feed: the chunk's nact_all[rows] / mult_all[rows, tb] and the fixed buffers the gathered row's values go to"""
+    _fields_ = [('nact_all', _vp), ('mult_all', _vp), ('n_act', _vp), ('task_w', _vp)]
+
+
+def _active_tasks(active):
+    """active = (n_act, task_w) tensors | None -> ActiveTasks | None"""
+    if active is None:
+        return None
+    n_act, task_w = active
+    assert n_act.dtype == torch.int32 and n_act.is_cuda and task_w.is_cuda
+    return ActiveTasks(n_act.data_ptr(), task_w.data_ptr())
+
+
+def _active_feed(feed):
+    """the ActiveFeed of an engine.StepFeed that deduplicates its draws, else None"""
+    if not getattr(feed, 'dedup', False):
+        return None
+    return ActiveFeed(feed.nact_all.data_ptr(), feed.mult_all.data_ptr(), feed.nact.data_ptr(), feed.mult.data_ptr())
+
+
+def _active_call(lib, name, act, *args):
+    """lib.<name>(*args), or with act (ActiveTasks / ActiveFeed) the call's distinct-task form lib.<name>_active(&act, *args)"""
+    if act is None:
+        return getattr(lib, name)(*args)
+    return getattr(lib, name + '_active')(ctypes.byref(act), *args)
 
 
 def reload_env():
@@ -429,7 +469,10 @@ def _gp_lml_dense(z, z_div, mean, mean_mode, y, y_div, lengthscale, outputscale,
 
 
 def gp_lml_fwdbwd(z, z_div, mean, mean_mode, y, y_div, lengthscale, outputscale, noise, B, P, n_valid=None,
-                  g_lml=None, want_dz=True, kernel=KERNEL_RBF):
+                  g_lml=None, want_dz=True, kernel=KERNEL_RBF, active=None):
+    """active = (n_act int32 [1], task_w [T]) in device memory: only the problems of the first n_act tasks are evaluated, their
+    gradients weighted by task_w (the distinct tasks of a draw with replacement; fp32, n <= 128, f <= 4, RBF); the outputs of the
+    other problems are left as allocated"""
     lib = load_library()
     n, f = z.shape[-2], z.shape[-1]
     dev, dt = z.device, z.dtype
@@ -446,10 +489,13 @@ def gp_lml_fwdbwd(z, z_div, mean, mean_mode, y, y_div, lengthscale, outputscale,
     d_noise = torch.empty(B, dtype=dt, device=dev)
     info = torch.empty(B, dtype=torch.int32, device=dev)
     if FORCE_DENSE or n > gp_small_max_n(dt, True):
+        if active is not None:
+            raise RuntimeError('the dense GP path has no distinct-task form')
         return _gp_lml_dense(z, z_div, mean, mean_mode, y, y_div, lengthscale, outputscale, noise, n_valid, g_lml, B, P, info,
                              True, want_dz, kernel=kernel) + (info,)
     with _Timed('gp_lml_fwdbwd'):
-        _check(lib.pacoh_gp_lml_fwdbwd(_ptr(z), z_div, _ptr(mean, z), mean_mode, _ptr(y, z), y_div, _ptr(lengthscale, z),
+        _check(_active_call(lib, 'pacoh_gp_lml_fwdbwd', _active_tasks(active),
+                                       _ptr(z), z_div, _ptr(mean, z), mean_mode, _ptr(y, z), y_div, _ptr(lengthscale, z),
                                        _ptr(outputscale, z), _ptr(noise, z), _ptr(n_valid), _ptr(g_lml, z), _ptr(lml),
                                        _ptr(d_z), _ptr(d_mean), _ptr(d_ls), _ptr(d_os), _ptr(d_noise), _ptr(info),
                                        B, P, n, _kf(f, kernel), dtype_code(z), _stream()), 'pacoh_gp_lml_fwdbwd')
@@ -599,12 +645,15 @@ def mlp2_stash(x, P, d_in, hidden, d_out_a, d_out_b, B, n, stash=None):
     return stash
 
 
-def mlp2_fwd(x, x_div, theta, P, d_in, hidden, off_a, d_out_a, off_b, d_out_b, B, n, ws_holder=None, stash=None, svgd_tail=None):
+def mlp2_fwd(x, x_div, theta, P, d_in, hidden, off_a, d_out_a, off_b, d_out_b, B, n, ws_holder=None, stash=None, svgd_tail=None,
+             active=None):
     """two networks of the same hidden shape (blocks at element offsets off_a / off_b of the rows of theta[P, D]) on the
     same inputs: -> (out_a[B,n,d_out_a], out_b[B,n,d_out_b]); one launch on the fused fp32 path.  stash (mlp2_stash()) receives
     the activations the matching mlp2_bwd(stash=...) would otherwise recompute.  svgd_tail = (particles, workspace, counter): the
-    pipelined SVGD step's distance matrix + counter increment ride in the same launch (svgd_dist_advance)"""
+    pipelined SVGD step's distance matrix + counter increment ride in the same launch (svgd_dist_advance).  active = (n_act, task_w):
+    only the rows of the first n_act tasks are computed (gp_lml_fwdbwd; fused fp32 networks only)"""
     lib = load_library()
+    act = _active_tasks(active)
     out_a = torch.empty(B, n, d_out_a, dtype=x.dtype, device=x.device)
     out_b = torch.empty(B, n, d_out_b, dtype=x.dtype, device=x.device)
     harr, code = _hidden_arr(hidden), dtype_code(x)
@@ -612,11 +661,13 @@ def mlp2_fwd(x, x_div, theta, P, d_in, hidden, off_a, d_out_a, off_b, d_out_b, B
     with _Timed('mlp_fwd'):
         if svgd_tail is not None:
             sv_X, sv_ws, ctr = svgd_tail
-            _check(lib.pacoh_mlp2_fwd_svgd(_ptr(x), x_div, _ptr(theta, x), theta.shape[1], P, d_in, harr, len(hidden), off_a, d_out_a,
+            _check(_active_call(lib, 'pacoh_mlp2_fwd_svgd', act,
+                                           _ptr(x), x_div, _ptr(theta, x), theta.shape[1], P, d_in, harr, len(hidden), off_a, d_out_a,
                                            _ptr(out_a), off_b, d_out_b, _ptr(out_b), _ptr(ws), _ptr(stash), B, n, _ptr(sv_X, x),
                                            _ptr(sv_ws), sv_X.shape[0], sv_X.shape[1], _ptr(ctr), code, _stream()), 'pacoh_mlp2_fwd_svgd')
         else:
-            _check(lib.pacoh_mlp2_fwd(_ptr(x), x_div, _ptr(theta, x), theta.shape[1], P, d_in, harr, len(hidden), off_a, d_out_a,
+            _check(_active_call(lib, 'pacoh_mlp2_fwd', act,
+                                      _ptr(x), x_div, _ptr(theta, x), theta.shape[1], P, d_in, harr, len(hidden), off_a, d_out_a,
                                       _ptr(out_a), off_b, d_out_b, _ptr(out_b), _ptr(ws), _ptr(stash), B, n, code, _stream()), 'pacoh_mlp2_fwd')
     return out_a, out_b
 
@@ -638,16 +689,18 @@ def mlp2_bwd(x, x_div, theta, P, d_in, hidden, off_a, d_out_a, g_a, off_b, d_out
 
 def mlp2_bwd_hyper(x, x_div, theta, P, d_in, hidden, off_a, d_out_a, g_a, off_b, d_out_b, g_b, d_theta, B, n, T, off_ls, f, off_os,
                    off_noise, off_const, d_ls, d_os, d_noise, d_const, lml=None, lik=None, lik_scale=1.0, info=None, fail_flag=None,
-                   workspace=None, stash=None, svgd_bw=None, opt=None):
+                   workspace=None, stash=None, svgd_bw=None, opt=None, active=None):
     """mlp2_bwd + hyper_bwd (grad = d_theta) in one C-ABI call: the gradient epilogue of a step; returns the workspace for reuse.
-    svgd_bw = (SVGD workspace, P, D): the step's median bandwidth is computed by one more workgroup (hyper_bwd)"""
+    svgd_bw = (SVGD workspace, P, D): the step's median bandwidth is computed by one more workgroup (hyper_bwd).
+    active = (n_act, task_w): as mlp2_fwd / gp_lml_fwdbwd -- the sums run over the first n_act tasks, lik weights lml by task_w"""
     lib = load_library()
     harr, code = _hidden_arr(hidden), dtype_code(x)
     need = lib.pacoh_mlp2_bwd_workspace_bytes(B, P, n, d_in, harr, len(hidden), d_out_a, d_out_b, code)
     if workspace is None or workspace.numel() * workspace.element_size() < need:
         workspace = torch.empty(max(1, need), dtype=torch.uint8, device=x.device)
     with _Timed('mlp_bwd'):
-        _check(lib.pacoh_mlp2_bwd_hyper(_ptr(x), x_div, _ptr(theta, x), theta.shape[1], P, d_in, harr, len(hidden), off_a, d_out_a,
+        _check(_active_call(lib, 'pacoh_mlp2_bwd_hyper', _active_tasks(active),
+                                        _ptr(x), x_div, _ptr(theta, x), theta.shape[1], P, d_in, harr, len(hidden), off_a, d_out_a,
                                         _ptr(g_a, x), off_b, d_out_b, _ptr(g_b, x), _ptr(d_theta, x), d_theta.shape[1], 0,
                                         _ptr(workspace), _ptr(stash), B, n, T, off_ls, f, off_os, off_noise, off_const,
                                         _ptr(d_ls, x), _ptr(d_os, x), _ptr(d_noise, x), _ptr(d_const, x), _ptr(lml, x), _ptr(lik, x),
@@ -1035,7 +1088,8 @@ def step_begin(feed, tasks, out, theta=None, hyper=None, hyper_out=None, advance
         ls, os_, noise = hyper_out
         P, stride = theta.shape
     with _Timed('step_begin'):
-        _check(lib.pacoh_step_begin(_ptr(feed.idx_all), tb, _ptr(feed.sc_all), feed.sc_all.shape[1], _ptr(feed.aux_all, feed.sc_all), n_aux,
+        _check(_active_call(lib, 'pacoh_step_begin', _active_feed(feed),
+                                    _ptr(feed.idx_all), tb, _ptr(feed.sc_all), feed.sc_all.shape[1], _ptr(feed.aux_all, feed.sc_all), n_aux,
                                     _ptr(feed.ctr), _ptr(feed.ticket), _ptr(feed.sc), _ptr(feed.aux, feed.sc_all),
                                     _ptr(x, feed.sc_all), _ptr(y, feed.sc_all), _ptr(nv), _ptr(ox), _ptr(oy), _ptr(onv), n, d,
                                     _ptr(theta, feed.sc_all), stride, P, off_ls, f, off_os, off_noise, float(floor), _ptr(ls), _ptr(os_),
@@ -1123,7 +1177,8 @@ def svgd_update_next(X, score, prior_mean, prior_std, prior_factor, bandwidth, o
     off_ls, f, off_os, off_noise, floor, kernel = hyper
     ls, os_, noise = feed.hyp
     with _Timed('svgd_phi'):
-        _check(lib.pacoh_svgd_update_next(_ptr(X), _ptr(score, X), _ptr(prior_mean, X), _ptr(prior_std, X), float(prior_factor), bw,
+        _check(_active_call(lib, 'pacoh_svgd_update_next', _active_feed(feed),
+                                          _ptr(X), _ptr(score, X), _ptr(prior_mean, X), _ptr(prior_std, X), float(prior_factor), bw,
                                           int(optimizer == 'Adam'), float(beta1), float(beta2), _ptr(exp_avg, X), _ptr(exp_avg_sq, X),
                                           _ptr(bw_out), _ptr(workspace), P, D,
                                           _ptr(feed.ctr), _ptr(feed.sc2, X), feed.sc2.shape[1], _ptr(feed.idx_all), feed.tb,

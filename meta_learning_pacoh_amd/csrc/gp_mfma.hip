@@ -32,6 +32,7 @@ struct GpMfmaArgs {
     float* lml; int32_t* info;
     float* d_z; float* d_mean; float* d_ls; float* d_os; float* d_noise;
     int B, P, n, f;
+    const int32_t* n_act; const float* task_w;      // (gp_reg_body.h: the register-resident kernel's distinct-task step)
 };
 
 #ifdef PACOH_GP_STAMPS

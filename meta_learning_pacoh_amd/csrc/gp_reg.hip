@@ -15,6 +15,11 @@ namespace pacoh {
 #define GPR_MINW(NB, FP, BWD) ((NB) > 4 ? ((FP) == 2 || (NB) == 6 ? 2 : 1) : ((NB) == 4 && (FP) == 4 ? ((BWD) ? 2 : 3) : 4))
 template <int NB, int FP, bool BWD, bool HAS_OS = true>
 __global__ void __launch_bounds__(64, GPR_MINW(NB, FP, BWD)) gp_reg_kernel(GpMfmaArgs a) {
+    // distinct-task step: the problems of tasks >= *n_act (b / P >= *n_act) are not evaluated -- before any LDS is touched; the
+    // pointer is read late from the kernel-argument segment like the body's output pointers (gpreg::KernelCtx)
+    if (const int32_t* n_act = gpreg::KernelCtx{}.late(a.n_act, (unsigned)__builtin_offsetof(GpMfmaArgs, n_act))) {
+        if (blockIdx.x >= (unsigned)*n_act * (unsigned)a.P) return;
+    }
     constexpr int NP = 16 * NB;
     constexpr int NU = NB * (NB + 1) / 2;
     __shared__ __attribute__((aligned(16))) float zf[NP * FP];      // features / lengthscale

@@ -42,6 +42,9 @@ struct GpMfmaArgs {            // (same struct as in gp_small.hip / gp_mfma.hip)
     float* lml; int32_t* info;
     float* d_z; float* d_mean; float* d_ls; float* d_os; float* d_noise;
     int B, P, n, f;
+    // distinct-task step (include/pacoh_gp.h, pacoh_active_tasks; gp_reg_kernel only, nullptr elsewhere): problems of tasks >= *n_act
+    // return at once, the upstream gradient of problem b is g_lml[b] * task_w[b / P]
+    const int32_t* n_act; const float* task_w;
 };
 
 // the test side of a posterior-predictive call (gp_reg_predict_kernel): test inputs [B / zt_div, m, f], the prior mean at them
@@ -219,6 +222,7 @@ __device__ __forceinline__ void factor16(f32x4 Cn, f32x4& Z, float& dprod, const
 // per problem.  The pointers only needed for the final stores are fetched from the kernel-argument segment at that point
 // instead (a scalar-cache hit).
 struct KernelCtx {
+    static constexpr bool TASK_WEIGHTS = true;     // (GpMfmaArgs::task_w is filled in by the caller: a host launch)
     __device__ __forceinline__ int lane() const { return threadIdx.x; }
     __device__ __forceinline__ unsigned block() const { return blockIdx.x; }
     template <typename T>
@@ -230,6 +234,7 @@ struct KernelCtx {
 };
 // A wave of a larger workgroup working on problem `b` of an argument block held by the caller (map_persist.hip)
 struct WaveCtx {
+    static constexpr bool TASK_WEIGHTS = false;    // (the argument block is built inside a kernel, field by field: no task weights there)
     unsigned b;
     __device__ __forceinline__ int lane() const { return threadIdx.x & 63; }
     __device__ __forceinline__ unsigned block() const { return b; }
@@ -584,7 +589,11 @@ __device__ __forceinline__ void gp_reg_body(const GpMfmaArgs& a, const Ctx& cx, 
     }
     // ---- gradient sums ---------------------------------------------------------------------------------------------------------------
     const float* g_lml_p = GPR_LATE(g_lml);
-    const float gup = g_lml_p ? g_lml_p[b] : 1.0f;
+    float gup = g_lml_p ? g_lml_p[b] : 1.0f;
+    if constexpr (Ctx::TASK_WEIGHTS && FAM == PACOH_KERNEL_RBF) {   // a task drawn c times: its problems are evaluated once and count c times
+        const float* task_w_p = GPR_LATE(task_w);
+        if (task_w_p) gup *= task_w_p[blk / (unsigned)a.P];
+    }
     const float osn = 0.5f * os * inv_nv;   // the outputscale rides on the 1/(2 n) factor: M_ij = G_ij os e_ij
     float msum = 0.0f, dnz = 0.0f;                              // sum of M (= os d lml/d os), os x trace part (= os d lml/d noise); x osn at the end
     // Every ordered pair (i, j) is visited, column block by column block: lane (r, g) holds the entries (i = 16I + 4g+s, j = 16J + r),

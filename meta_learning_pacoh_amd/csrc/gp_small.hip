@@ -387,6 +387,7 @@ struct GpMfmaArgs {
     float* lml; int32_t* info;
     float* d_z; float* d_mean; float* d_ls; float* d_os; float* d_noise;
     int B, P, n, f;
+    const int32_t* n_act; const float* task_w;      // (gp_reg_body.h: the register-resident kernel's distinct-task step)
 };
 int gp_mfma_try(const GpMfmaArgs& a, bool bwd, hipStream_t s);
 int gp_reg_try(const GpMfmaArgs& a, bool bwd, hipStream_t s);      // register-resident kernel (gp_reg.hip): n <= 64, f <= 4
@@ -401,7 +402,8 @@ int gp_reg_predict_try(const GpMfmaArgs& a, const GpPredArgs& pa, hipStream_t s)
 int gp_reg_matern_try(const GpMfmaArgs& a, int kind, bool bwd, hipStream_t s);                        // the same for the Matern
 int gp_reg_matern_predict_try(const GpMfmaArgs& a, const GpPredArgs& pa, int kind, hipStream_t s);    // families (gp_reg_matern.hip)
 }
-static int try_mfma(const GpArgs<float>& a, bool bwd, hipStream_t s) {
+// act (distinct-task step): only the register-resident RBF kernel takes it -- PACOH_ELIMIT where the shape goes elsewhere
+static int try_mfma(const GpArgs<float>& a, bool bwd, hipStream_t s, const pacoh_active_tasks* act = nullptr) {
     // (the register-resident kernels evaluate the RBF and Matern families, the LDS-resident MFMA kernels RBF only; cosine: general kernel)
     if (a.kind != PACOH_KERNEL_RBF && !family_matern(a.kind)) return 1;
     if (a.n > 128 || a.B <= 0 || a.P <= 0 || a.f <= 0 || a.f > PACOH_MAX_FEATURES ||
@@ -409,6 +411,11 @@ static int try_mfma(const GpArgs<float>& a, bool bwd, hipStream_t s) {
         return 1;
     GpMfmaArgs m = {a.z, a.z_div, a.mean, a.mean_mode, a.y, a.y_div, a.ls, a.os, a.noise, a.n_valid, a.g_lml,
                     a.lml, a.info, a.d_z, a.d_mean, a.d_ls, a.d_os, a.d_noise, a.B, a.P, a.n, a.f};
+    if (act) {
+        if (!bwd || a.kind != PACOH_KERNEL_RBF || a.n > 128 || a.f > 4 || a.n < 1) return PACOH_ELIMIT;
+        m.n_act = act->n_act; m.task_w = (const float*)act->task_w;
+        return gp_reg_try(m, true, s);
+    }
     // the forward-only entry points may ask for alpha / L outputs, which only the LDS-resident kernels produce: they do not come here
     if (family_matern(a.kind)) return gp_reg_matern_try(m, a.kind, bwd, s);     // (1 for 4 < f: the general kernel)
     const int rc = gp_reg_try(m, bwd, s);
@@ -450,25 +457,48 @@ extern "C" int pacoh_gp_lml_fwd(const void* z, int z_div, const void* mean, int 
     return launch_gp_small<double, MODE_FWD>(a, (hipStream_t)stream);
 }
 
-extern "C" int pacoh_gp_lml_fwdbwd(const void* z, int z_div, const void* mean, int mean_mode,
-                                   const void* y, int y_div, const void* lengthscale, const void* outputscale,
-                                   const void* noise, const int32_t* n_valid, const void* g_lml,
-                                   void* lml, void* d_z, void* d_mean, void* d_lengthscale,
-                                   void* d_outputscale, void* d_noise, int32_t* info,
-                                   int B, int P, int n, int f, int dtype, void* stream) {
+static int gp_lml_fwdbwd_impl(const pacoh_active_tasks* act, const void* z, int z_div, const void* mean, int mean_mode,
+                              const void* y, int y_div, const void* lengthscale, const void* outputscale,
+                              const void* noise, const int32_t* n_valid, const void* g_lml,
+                              void* lml, void* d_z, void* d_mean, void* d_lengthscale,
+                              void* d_outputscale, void* d_noise, int32_t* info,
+                              int B, int P, int n, int f, int dtype, void* stream) {
     if (check_dtype(dtype)) return PACOH_EDTYPE;
     if (!lml || !d_lengthscale || !d_noise) return PACOH_EINVAL;
+    if (act && (!act->n_act || !act->task_w)) return PACOH_EINVAL;
+    if (act && dtype != PACOH_F32) return PACOH_ELIMIT;
     if (dtype == PACOH_F32) {
         auto a = make_args<float>(z, z_div, mean, mean_mode, y, y_div, lengthscale, outputscale, noise, n_valid, B, P, n, f);
         a.g_lml = (const float*)g_lml; a.lml = (float*)lml; a.d_z = (float*)d_z; a.d_mean = (float*)d_mean;
         a.d_ls = (float*)d_lengthscale; a.d_os = (float*)d_outputscale; a.d_noise = (float*)d_noise; a.info = info;
-        { int rc = try_mfma(a, true, (hipStream_t)stream); if (rc != 1) return rc; }
+        { int rc = try_mfma(a, true, (hipStream_t)stream, act); if (rc != 1) return rc; }
+        if (act) return PACOH_ELIMIT;                      // (no kernel of this shape skips tasks: never evaluate them all unasked)
         return launch_gp_small<float, MODE_FWDBWD>(a, (hipStream_t)stream);
     }
     auto a = make_args<double>(z, z_div, mean, mean_mode, y, y_div, lengthscale, outputscale, noise, n_valid, B, P, n, f);
     a.g_lml = (const double*)g_lml; a.lml = (double*)lml; a.d_z = (double*)d_z; a.d_mean = (double*)d_mean;
     a.d_ls = (double*)d_lengthscale; a.d_os = (double*)d_outputscale; a.d_noise = (double*)d_noise; a.info = info;
     return launch_gp_small<double, MODE_FWDBWD>(a, (hipStream_t)stream);
+}
+
+extern "C" int pacoh_gp_lml_fwdbwd(const void* z, int z_div, const void* mean, int mean_mode,
+                                   const void* y, int y_div, const void* lengthscale, const void* outputscale,
+                                   const void* noise, const int32_t* n_valid, const void* g_lml,
+                                   void* lml, void* d_z, void* d_mean, void* d_lengthscale,
+                                   void* d_outputscale, void* d_noise, int32_t* info,
+                                   int B, int P, int n, int f, int dtype, void* stream) {
+    return gp_lml_fwdbwd_impl(nullptr, z, z_div, mean, mean_mode, y, y_div, lengthscale, outputscale, noise, n_valid, g_lml, lml, d_z, d_mean,
+                              d_lengthscale, d_outputscale, d_noise, info, B, P, n, f, dtype, stream);
+}
+// ... of a distinct-task step (include/pacoh_gp.h, pacoh_active_tasks)
+extern "C" int pacoh_gp_lml_fwdbwd_active(const pacoh_active_tasks* act, const void* z, int z_div, const void* mean, int mean_mode,
+                                          const void* y, int y_div, const void* lengthscale, const void* outputscale,
+                                          const void* noise, const int32_t* n_valid, const void* g_lml,
+                                          void* lml, void* d_z, void* d_mean, void* d_lengthscale,
+                                          void* d_outputscale, void* d_noise, int32_t* info,
+                                          int B, int P, int n, int f, int dtype, void* stream) {
+    return gp_lml_fwdbwd_impl(act, z, z_div, mean, mean_mode, y, y_div, lengthscale, outputscale, noise, n_valid, g_lml, lml, d_z, d_mean,
+                              d_lengthscale, d_outputscale, d_noise, info, B, P, n, f, dtype, stream);
 }
 
 extern "C" size_t pacoh_gp_predict_workspace_bytes(int B, int n, int m, int dtype, int want_cov) {

@@ -70,6 +70,8 @@ struct HyperBwdArgs {
     AdamInline<T> opt;                       // PACOH-MAP at world size 1: the AdamW step on every entry this reduction finishes
     StepNextArgs<T> nx;                      // ... and the pipelined feed: the updated hyper-parameters' transforms are published by the
                                              // blocks that update them, tb + 1 more virtual blocks fetch the next step's operands
+    const int32_t* n_act; const T* task_w;   // distinct-task step (pacoh_active_tasks): the sums run over the first *n_act tasks -- the GP
+                                             // kernel has weighted their gradients by task_w --, the likelihood sum applies task_w itself
 };
 
 // virtual blocks of the reduction itself, and with the optional bandwidth block behind them
@@ -84,15 +86,17 @@ template <typename T> __device__ __forceinline__ T hyper_sigmoid(T x) { return x
 template <typename T>
 __device__ __forceinline__ void hyper_bwd_block(const HyperBwdArgs<T>& a, int w, T* red) {
     const int per = a.f + 4;
+    int Tt = a.Tt;
+    if (a.n_act) { const int live = *a.n_act; Tt = live < Tt ? live : Tt; }
     // the step's numerical status rides along: any problem whose jittered Cholesky failed (info < 0) raises the caller's flag
     // (gpytorch's psd_safe_cholesky raises NotPSDError at that point; the host checks the flag at its next synchronisation)
     if (a.info && a.fail_flag && w % per == a.f + 1) {
         const int pp = w / per;
         bool bad = false;
-        for (int t0 = threadIdx.x; t0 < a.Tt; t0 += 4 * 256) {
+        for (int t0 = threadIdx.x; t0 < Tt; t0 += 4 * 256) {
             int v[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) { const int t = t0 + 256 * u; v[u] = a.info[(long)(t < a.Tt ? t : a.Tt - 1) * a.P + pp]; }
+            for (int u = 0; u < 4; ++u) { const int t = t0 + 256 * u; v[u] = a.info[(long)(t < Tt ? t : Tt - 1) * a.P + pp]; }
 #pragma unroll
             for (int u = 0; u < 4; ++u) bad |= v[u] < 0;      // (a clamped copy of the last task's value: the same verdict)
         }
@@ -114,15 +118,20 @@ __device__ __forceinline__ void hyper_bwd_block(const HyperBwdArgs<T>& a, int w,
     if (ncol == 1) {
         // (four tasks per trip, their loads requested together, added in the same order: one task per trip was one memory round trip
         //  per 256 tasks -- four in a row at cfg #3's 1 024 tasks per step)
-        for (int t0 = threadIdx.x; t0 < a.Tt; t0 += 4 * 256) {
+        const T* tw = (e == a.f + 3) ? a.task_w : nullptr;      // (the likelihood sum: lml is per task, not per draw)
+        for (int t0 = threadIdx.x; t0 < Tt; t0 += 4 * 256) {
             T v[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) { const int t = t0 + 256 * u; v[u] = src[((long)(t < a.Tt ? t : a.Tt - 1) * a.P + p) * width + col]; }
+            for (int u = 0; u < 4; ++u) {
+                const int t = t0 + 256 * u, tc = t < Tt ? t : Tt - 1;
+                v[u] = src[((long)tc * a.P + p) * width + col];
+                if (tw) v[u] *= tw[tc];
+            }
 #pragma unroll
-            for (int u = 0; u < 4; ++u) if (t0 + 256 * u < a.Tt) s += v[u];
+            for (int u = 0; u < 4; ++u) if (t0 + 256 * u < Tt) s += v[u];
         }
     } else {
-        for (int t = threadIdx.x; t < a.Tt; t += 256)
+        for (int t = threadIdx.x; t < Tt; t += 256)
             for (int c = 0; c < ncol; ++c) s += src[((long)t * a.P + p) * width + col + c];
     }
     s = subwave_sum<T>(s, 64);

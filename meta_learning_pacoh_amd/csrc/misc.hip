@@ -585,6 +585,9 @@ struct StepBeginArgs {
     // the step's noise row (aux_all[row], NOT the copy another block of this launch is making), their log q, and the transformed
     // hyper-parameters of the samples -- pacoh_vi_sample + pacoh_hyper_fwd without their launches
     const T* vi_post; T* vi_theta; T* vi_logq; int vi_S, vi_D;
+    // distinct-task feed (step_tail.h, StepNextArgs): the row's count of distinct tasks and their multiplicities, published by the
+    // blocks that gather the tasks / copy the scalars
+    const int32_t* nact_all; const T* mult_all; int32_t* o_nact; T* o_mult;
 };
 
 template <typename T, int NT>
@@ -600,8 +603,10 @@ __global__ void __launch_bounds__(NT) step_begin_kernel(StepBeginArgs<T> a) {
         for (int q = threadIdx.x; q < a.nx; q += NT) dx[q] = sx[q];
         for (int q = threadIdx.x; q < a.ny; q += NT) dy[q] = sy[q];
         if (threadIdx.x == 0 && a.n_valid) a.onv[blk] = a.n_valid[t];
+        if (threadIdx.x == 0 && a.nact_all) a.o_mult[blk] = a.mult_all[row * a.tb + blk];
     } else if (blk == a.tb) {
         for (int q = threadIdx.x; q < a.n_sc; q += NT) a.sc_out[q] = a.sc_all[row * a.n_sc + q];
+        if (threadIdx.x == 0 && a.nact_all) *a.o_nact = a.nact_all[row];
     } else if (blk == a.tb + 1) {
         if (a.theta) {
             const int per = a.f + 2;
@@ -703,7 +708,8 @@ static int step_begin_launch(const int64_t* idx_all, int tb, const void* sc_all,
                              void* out_y, int32_t* out_n_valid, int n, int d, const void* theta, long theta_stride, int P, int off_ls, int f,
                              int off_os, int off_noise, double noise_floor, void* ls, void* os, void* noise, int advance,
                              const void* svgd_X, void* svgd_workspace, int svgd_P, int svgd_D, hipStream_t s,
-                             const void* vi_post = nullptr, void* vi_theta = nullptr, void* vi_logq = nullptr, int vi_S = 0, int vi_D = 0) {
+                             const void* vi_post = nullptr, void* vi_theta = nullptr, void* vi_logq = nullptr, int vi_S = 0, int vi_D = 0,
+                             const pacoh_active_feed* feed = nullptr) {
     long ab = n_aux > 0 ? (n_aux + 2047) / 2048 : 0;
     if (ab > 256) ab = 256;
     T* d2 = (T*)svgd_workspace;                       // (layout of pacoh_svgd_update_dev_workspace_bytes: distances | snapshot | median pair)
@@ -711,7 +717,9 @@ static int step_begin_launch(const int64_t* idx_all, int tb, const void* sc_all,
                           (T*)aux_out, (const T*)x, (const T*)y, n_valid, (T*)out_x, (T*)out_y, out_n_valid, n * d, n, (const T*)theta,
                           theta_stride, P, off_ls, features_of(f), off_os, off_noise, (T)noise_floor, (T*)ls, (T*)os, (T*)noise,
                           (int)ab, (const T*)svgd_X, d2, svgd_X ? d2 + svgd_P * svgd_P : nullptr, svgd_P, svgd_D,
-                          ties_scale(f), (const T*)vi_post, (T*)vi_theta, (T*)vi_logq, vi_S, vi_D};
+                          ties_scale(f), (const T*)vi_post, (T*)vi_theta, (T*)vi_logq, vi_S, vi_D,
+                          feed ? feed->nact_all : nullptr, feed ? (const T*)feed->mult_all : nullptr, feed ? feed->n_act : nullptr,
+                          feed ? (T*)feed->task_w : nullptr};
     const long sb = svgd_X ? (long)svgd_P * svgd_P : 0;
     const dim3 grid((unsigned)(tb + 2 + ab + sb + (vi_post ? vi_S : 0)));
     if (vi_post && vi_sample_nt(vi_D) == 1024) hipLaunchKernelGGL((step_begin_kernel<T, 1024>), grid, dim3(1024), 0, s, a);
@@ -720,13 +728,18 @@ static int step_begin_launch(const int64_t* idx_all, int tb, const void* sc_all,
     return launch_status();
 }
 
-extern "C" int pacoh_step_begin(const int64_t* idx_all, int tb, const void* sc_all, int n_sc, const void* aux_all, long n_aux,
-                                int64_t* counter, int32_t* ticket, void* sc_out, void* aux_out,
-                                const void* x, const void* y, const int32_t* n_valid, void* out_x, void* out_y, int32_t* out_n_valid, int n, int d,
-                                const void* theta, long theta_stride, int P, int off_ls, int f, int off_os, int off_noise, double noise_floor,
-                                void* ls, void* os, void* noise, int advance, const void* svgd_X, void* svgd_workspace, int svgd_P, int svgd_D,
-                                int dtype, void* stream) {
+static bool active_feed_ok(const pacoh_active_feed* feed, int tb) {
+    return feed->nact_all && feed->mult_all && feed->n_act && feed->task_w && tb > 0;
+}
+
+static int step_begin_impl(const pacoh_active_feed* feed, const int64_t* idx_all, int tb, const void* sc_all, int n_sc, const void* aux_all,
+                           long n_aux, int64_t* counter, int32_t* ticket, void* sc_out, void* aux_out,
+                           const void* x, const void* y, const int32_t* n_valid, void* out_x, void* out_y, int32_t* out_n_valid, int n, int d,
+                           const void* theta, long theta_stride, int P, int off_ls, int f, int off_os, int off_noise, double noise_floor,
+                           void* ls, void* os, void* noise, int advance, const void* svgd_X, void* svgd_workspace, int svgd_P, int svgd_D,
+                           int dtype, void* stream) {
     if (check_dtype(dtype)) return PACOH_EDTYPE;
+    if (feed && !active_feed_ok(feed, tb)) return PACOH_EINVAL;
     if (!counter || !ticket || tb < 0 || n_sc < 0 || n_aux < 0 || (n_sc > 0 && (!sc_all || !sc_out)) || (n_aux > 0 && (!aux_all || !aux_out)))
         return PACOH_EINVAL;
     if (tb > 0 && (!idx_all || !x || !y || !out_x || !out_y || n <= 0 || d <= 0 || (n_valid == nullptr) != (out_n_valid == nullptr))) return PACOH_EINVAL;
@@ -736,10 +749,31 @@ extern "C" int pacoh_step_begin(const int64_t* idx_all, int tb, const void* sc_a
     if (dtype == PACOH_F32)
         return step_begin_launch<float>(idx_all, tb, sc_all, n_sc, aux_all, n_aux, counter, ticket, sc_out, aux_out, x, y, n_valid, out_x, out_y,
                                         out_n_valid, n, d, theta, theta_stride, P, off_ls, f, off_os, off_noise, noise_floor, ls, os, noise,
-                                        advance, svgd_X, svgd_workspace, svgd_P, svgd_D, (hipStream_t)stream);
+                                        advance, svgd_X, svgd_workspace, svgd_P, svgd_D, (hipStream_t)stream, nullptr, nullptr, nullptr, 0, 0, feed);
     return step_begin_launch<double>(idx_all, tb, sc_all, n_sc, aux_all, n_aux, counter, ticket, sc_out, aux_out, x, y, n_valid, out_x, out_y,
                                      out_n_valid, n, d, theta, theta_stride, P, off_ls, f, off_os, off_noise, noise_floor, ls, os, noise,
-                                     advance, svgd_X, svgd_workspace, svgd_P, svgd_D, (hipStream_t)stream);
+                                     advance, svgd_X, svgd_workspace, svgd_P, svgd_D, (hipStream_t)stream, nullptr, nullptr, nullptr, 0, 0, feed);
+}
+extern "C" int pacoh_step_begin(const int64_t* idx_all, int tb, const void* sc_all, int n_sc, const void* aux_all, long n_aux,
+                                int64_t* counter, int32_t* ticket, void* sc_out, void* aux_out,
+                                const void* x, const void* y, const int32_t* n_valid, void* out_x, void* out_y, int32_t* out_n_valid, int n, int d,
+                                const void* theta, long theta_stride, int P, int off_ls, int f, int off_os, int off_noise, double noise_floor,
+                                void* ls, void* os, void* noise, int advance, const void* svgd_X, void* svgd_workspace, int svgd_P, int svgd_D,
+                                int dtype, void* stream) {
+    return step_begin_impl(nullptr, idx_all, tb, sc_all, n_sc, aux_all, n_aux, counter, ticket, sc_out, aux_out, x, y, n_valid, out_x, out_y,
+                           out_n_valid, n, d, theta, theta_stride, P, off_ls, f, off_os, off_noise, noise_floor, ls, os, noise, advance, svgd_X,
+                           svgd_workspace, svgd_P, svgd_D, dtype, stream);
+}
+// ... with the distinct-task feed (include/pacoh_gp.h, pacoh_active_feed): the row's nact / mult entries go to the fixed buffers too
+extern "C" int pacoh_step_begin_active(const pacoh_active_feed* feed, const int64_t* idx_all, int tb, const void* sc_all, int n_sc,
+                                       const void* aux_all, long n_aux, int64_t* counter, int32_t* ticket, void* sc_out, void* aux_out,
+                                       const void* x, const void* y, const int32_t* n_valid, void* out_x, void* out_y, int32_t* out_n_valid,
+                                       int n, int d, const void* theta, long theta_stride, int P, int off_ls, int f, int off_os, int off_noise,
+                                       double noise_floor, void* ls, void* os, void* noise, int advance, const void* svgd_X,
+                                       void* svgd_workspace, int svgd_P, int svgd_D, int dtype, void* stream) {
+    return step_begin_impl(feed, idx_all, tb, sc_all, n_sc, aux_all, n_aux, counter, ticket, sc_out, aux_out, x, y, n_valid, out_x, out_y,
+                           out_n_valid, n, d, theta, theta_stride, P, off_ls, f, off_os, off_noise, noise_floor, ls, os, noise, advance, svgd_X,
+                           svgd_workspace, svgd_P, svgd_D, dtype, stream);
 }
 
 // pacoh_step_begin for a PACOH-VI step with a diagonal posterior: additionally draws the step's S samples theta[S, D] = loc +
@@ -989,15 +1023,16 @@ static int svgd_update_next_launch(void* X, const void* score, const void* mu, c
 // pacoh_svgd_update_dev for the pipelined step (step_tail.h): distances already in the workspace, scalars from the ping-pong rows
 // the counter selects, the updated particles' transformed hyper-parameters written by the update itself, and -- in extra workgroups
 // of the same launch -- the NEXT step's scalars and task batch fetched
-extern "C" int pacoh_svgd_update_next(void* X, const void* score, const void* prior_mean, const void* prior_std, double prior_factor,
-                                      double bandwidth, int use_adam, double beta1, double beta2, void* exp_avg, void* exp_avg_sq,
-                                      void* bw_out, void* workspace, int P, int D,
-                                      const int64_t* counter, void* sc2, int n_sc, const int64_t* idx_all, int tb, const void* sc_all,
-                                      const void* x, const void* y, const int32_t* n_valid, void* out_x, void* out_y,
-                                      int32_t* out_n_valid, int n, int d,
-                                      int off_ls, int f, int off_os, int off_noise, double noise_floor, void* ls, void* os, void* noise,
-                                      int bandwidth_ready, int dtype, void* stream) {
+static int svgd_update_next_impl(const pacoh_active_feed* feed, void* X, const void* score, const void* prior_mean, const void* prior_std,
+                                 double prior_factor, double bandwidth, int use_adam, double beta1, double beta2, void* exp_avg,
+                                 void* exp_avg_sq, void* bw_out, void* workspace, int P, int D,
+                                 const int64_t* counter, void* sc2, int n_sc, const int64_t* idx_all, int tb, const void* sc_all,
+                                 const void* x, const void* y, const int32_t* n_valid, void* out_x, void* out_y,
+                                 int32_t* out_n_valid, int n, int d,
+                                 int off_ls, int f, int off_os, int off_noise, double noise_floor, void* ls, void* os, void* noise,
+                                 int bandwidth_ready, int dtype, void* stream) {
     if (check_dtype(dtype)) return PACOH_EDTYPE;
+    if (feed && !active_feed_ok(feed, tb)) return PACOH_EINVAL;
     if (bandwidth_ready && P > 64) return PACOH_ELIMIT;
     if (!X || !score || !workspace || P <= 0 || D <= 0 || !counter || !sc2 || !sc_all || n_sc < PACOH_SC_COUNT) return PACOH_EINVAL;
     if ((prior_mean == nullptr) != (prior_std == nullptr)) return PACOH_EINVAL;
@@ -1012,16 +1047,45 @@ extern "C" int pacoh_svgd_update_next(void* X, const void* score, const void* pr
         StepNextArgs<float> nx = {(const long*)counter, (float*)sc2, n_sc, (const long*)idx_all, tb, (const float*)sc_all, (const float*)x,
                                   (const float*)y, n_valid, (float*)out_x, (float*)out_y, out_n_valid, n * d, n, off_ls, fdim, off_os, off_noise,
                                   ties_scale(f), (float)noise_floor, (float*)ls, (float*)os, (float*)noise,
-                                  bandwidth_ready ? (const float*)workspace + svgd_bw_slot(P, D) : nullptr};
+                                  bandwidth_ready ? (const float*)workspace + svgd_bw_slot(P, D) : nullptr,
+                                  feed ? feed->nact_all : nullptr, feed ? (const float*)feed->mult_all : nullptr,
+                                  feed ? feed->n_act : nullptr, feed ? (float*)feed->task_w : nullptr};
         return svgd_update_next_launch<float>(X, score, prior_mean, prior_std, prior_factor, bandwidth, use_adam, beta1, beta2, exp_avg,
                                               exp_avg_sq, bw_out, workspace, P, D, nx, (hipStream_t)stream);
     }
     StepNextArgs<double> nx = {(const long*)counter, (double*)sc2, n_sc, (const long*)idx_all, tb, (const double*)sc_all, (const double*)x,
                                (const double*)y, n_valid, (double*)out_x, (double*)out_y, out_n_valid, n * d, n, off_ls, fdim, off_os, off_noise,
                                ties_scale(f), noise_floor, (double*)ls, (double*)os, (double*)noise,
-                               bandwidth_ready ? (const double*)workspace + svgd_bw_slot(P, D) : nullptr};
+                               bandwidth_ready ? (const double*)workspace + svgd_bw_slot(P, D) : nullptr,
+                               feed ? feed->nact_all : nullptr, feed ? (const double*)feed->mult_all : nullptr,
+                               feed ? feed->n_act : nullptr, feed ? (double*)feed->task_w : nullptr};
     return svgd_update_next_launch<double>(X, score, prior_mean, prior_std, prior_factor, bandwidth, use_adam, beta1, beta2, exp_avg,
                                            exp_avg_sq, bw_out, workspace, P, D, nx, (hipStream_t)stream);
+}
+extern "C" int pacoh_svgd_update_next(void* X, const void* score, const void* prior_mean, const void* prior_std, double prior_factor,
+                                      double bandwidth, int use_adam, double beta1, double beta2, void* exp_avg, void* exp_avg_sq,
+                                      void* bw_out, void* workspace, int P, int D,
+                                      const int64_t* counter, void* sc2, int n_sc, const int64_t* idx_all, int tb, const void* sc_all,
+                                      const void* x, const void* y, const int32_t* n_valid, void* out_x, void* out_y,
+                                      int32_t* out_n_valid, int n, int d,
+                                      int off_ls, int f, int off_os, int off_noise, double noise_floor, void* ls, void* os, void* noise,
+                                      int bandwidth_ready, int dtype, void* stream) {
+    return svgd_update_next_impl(nullptr, X, score, prior_mean, prior_std, prior_factor, bandwidth, use_adam, beta1, beta2, exp_avg, exp_avg_sq,
+                                 bw_out, workspace, P, D, counter, sc2, n_sc, idx_all, tb, sc_all, x, y, n_valid, out_x, out_y, out_n_valid, n, d,
+                                 off_ls, f, off_os, off_noise, noise_floor, ls, os, noise, bandwidth_ready, dtype, stream);
+}
+// ... with the distinct-task feed (include/pacoh_gp.h, pacoh_active_feed): the tail publishes the next row's nact / mult entries too
+extern "C" int pacoh_svgd_update_next_active(const pacoh_active_feed* feed, void* X, const void* score, const void* prior_mean,
+                                             const void* prior_std, double prior_factor, double bandwidth, int use_adam, double beta1,
+                                             double beta2, void* exp_avg, void* exp_avg_sq, void* bw_out, void* workspace, int P, int D,
+                                             const int64_t* counter, void* sc2, int n_sc, const int64_t* idx_all, int tb, const void* sc_all,
+                                             const void* x, const void* y, const int32_t* n_valid, void* out_x, void* out_y,
+                                             int32_t* out_n_valid, int n, int d,
+                                             int off_ls, int f, int off_os, int off_noise, double noise_floor, void* ls, void* os, void* noise,
+                                             int bandwidth_ready, int dtype, void* stream) {
+    return svgd_update_next_impl(feed, X, score, prior_mean, prior_std, prior_factor, bandwidth, use_adam, beta1, beta2, exp_avg, exp_avg_sq,
+                                 bw_out, workspace, P, D, counter, sc2, n_sc, idx_all, tb, sc_all, x, y, n_valid, out_x, out_y, out_n_valid, n, d,
+                                 off_ls, f, off_os, off_noise, noise_floor, ls, os, noise, bandwidth_ready, dtype, stream);
 }
 
 template <typename T>

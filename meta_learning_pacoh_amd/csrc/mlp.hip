@@ -22,7 +22,7 @@ bool mlp_mfma_applicable(int d_in, const int32_t* hidden, int n_hidden, int d_ou
 bool mlp_fused_applicable(int d_in, const int32_t* hidden, int n_hidden, int d_out);
 int mlp_fused_fwd(const void* x, int x_div, const void* theta, long theta_stride, int P, int d_in, const int32_t* hidden,
                   int n_hidden, int nets, const long* off, const int* d_out, void* const* out, void* stash, int B, int n,
-                  hipStream_t s, const SvgdDistTail<float>* tail = nullptr, bool* tail_taken = nullptr);
+                  hipStream_t s, const SvgdDistTail<float>* tail = nullptr, bool* tail_taken = nullptr, const int32_t* n_act = nullptr);
 size_t mlp_fused_stash_bytes(int B, int P, int n, int n_hidden, int nets);
 size_t mlp_fused_bwd_workspace(int B, int P, int n, int d_in, const int32_t* hidden, int n_hidden, int d_out, int nets);
 int mlp_fused_bwd(const void* x, int x_div, const void* theta, long theta_stride, int P, int d_in, const int32_t* hidden,
@@ -185,8 +185,9 @@ extern "C" size_t pacoh_mlp2_stash_bytes(int B, int P, int n, int d_in, const in
 static int mlp2_fwd_impl(const void* x, int x_div, const void* theta, long theta_stride, int P, int d_in,
                          const int32_t* hidden, int n_hidden, long off_a, int d_out_a, void* out_a, long off_b, int d_out_b,
                          void* out_b, void* workspace, void* stash, int B, int n, int dtype, void* stream,
-                         const SvgdDistTail<float>* tail, bool* tail_done) {
+                         const SvgdDistTail<float>* tail, bool* tail_done, const pacoh_active_tasks* act = nullptr) {
     if (check_dtype(dtype)) return PACOH_EDTYPE;
+    if (act && !act->n_act) return PACOH_EINVAL;
     if (!out_a || !out_b || !x || !theta || x_div <= 0 || P <= 0 || B <= 0 || n <= 0 || B % P != 0 || off_a < 0 || off_b < 0) return PACOH_EINVAL;
     int rc = args_ok(d_in, hidden, n_hidden, d_out_a);
     if (rc || (rc = args_ok(d_in, hidden, n_hidden, d_out_b))) return rc;
@@ -196,8 +197,9 @@ static int mlp2_fwd_impl(const void* x, int x_div, const void* theta, long theta
         const int dout[2] = {d_out_a, d_out_b};
         void* const outs[2] = {out_a, out_b};
         return mlp_fused_fwd(x, x_div, theta, theta_stride, P, d_in, hidden, n_hidden, 2, off, dout, outs, stash, B, n, (hipStream_t)stream, tail,
-                             tail_done);
+                             tail_done, act ? act->n_act : nullptr);
     }
+    if (act) return PACOH_ELIMIT;                          // (only the fused kernels skip tasks)
     const size_t es = dtype == PACOH_F64 ? 8 : 4;
     void* st_a = nullptr; void* st_b = nullptr;          // the layer-by-layer path's per-network stashes (pacoh_mlp2_stash_bytes)
     if (stash && pick_path(dtype, d_in, hidden, n_hidden, d_out_a, (long)B * n) == PATH_LAYERS &&
@@ -216,17 +218,24 @@ extern "C" int pacoh_mlp2_fwd(const void* x, int x_div, const void* theta, long 
     return mlp2_fwd_impl(x, x_div, theta, theta_stride, P, d_in, hidden, n_hidden, off_a, d_out_a, out_a, off_b, d_out_b, out_b, workspace,
                          stash, B, n, dtype, stream, nullptr, nullptr);
 }
+// ... of a distinct-task step (include/pacoh_gp.h, pacoh_active_tasks)
+extern "C" int pacoh_mlp2_fwd_active(const pacoh_active_tasks* act, const void* x, int x_div, const void* theta, long theta_stride, int P,
+                                     int d_in, const int32_t* hidden, int n_hidden, long off_a, int d_out_a, void* out_a, long off_b,
+                                     int d_out_b, void* out_b, void* workspace, void* stash, int B, int n, int dtype, void* stream) {
+    return mlp2_fwd_impl(x, x_div, theta, theta_stride, P, d_in, hidden, n_hidden, off_a, d_out_a, out_a, off_b, d_out_b, out_b, workspace,
+                         stash, B, n, dtype, stream, nullptr, nullptr, act);
+}
 
 extern "C" int pacoh_svgd_dist_advance(const void* X, void* workspace, int P, int D, int64_t* counter, int dtype, void* stream);
 
 // pacoh_mlp2_fwd + pacoh_svgd_dist_advance: the first launch of a pipelined SVGD step (step_tail.h).  On the fused fp32 path the
 // particles' distance matrix, their snapshot and the step counter's increment run in extra workgroups of the forward launch;
 // elsewhere the two calls in sequence.
-extern "C" int pacoh_mlp2_fwd_svgd(const void* x, int x_div, const void* theta, long theta_stride, int P, int d_in,
-                                   const int32_t* hidden, int n_hidden, long off_a, int d_out_a, void* out_a, long off_b, int d_out_b,
-                                   void* out_b, void* workspace, void* stash, int B, int n,
-                                   const void* svgd_X, void* svgd_workspace, int svgd_P, int svgd_D, int64_t* counter,
-                                   int dtype, void* stream) {
+static int mlp2_fwd_svgd_impl(const pacoh_active_tasks* act, const void* x, int x_div, const void* theta, long theta_stride, int P, int d_in,
+                              const int32_t* hidden, int n_hidden, long off_a, int d_out_a, void* out_a, long off_b, int d_out_b,
+                              void* out_b, void* workspace, void* stash, int B, int n,
+                              const void* svgd_X, void* svgd_workspace, int svgd_P, int svgd_D, int64_t* counter,
+                              int dtype, void* stream) {
     if (!svgd_X || !svgd_workspace || svgd_P <= 0 || svgd_D <= 0) return PACOH_EINVAL;
     if (svgd_P > PACOH_SVGD_MAX_PARTICLES) return PACOH_ELIMIT;
     bool tail_done = false;
@@ -235,13 +244,29 @@ extern "C" int pacoh_mlp2_fwd_svgd(const void* x, int x_div, const void* theta, 
         float* d2 = (float*)svgd_workspace;
         SvgdDistTail<float> tail = {(const float*)svgd_X, d2, d2 + svgd_P * svgd_P, svgd_P, svgd_D, (long*)counter};
         rc = mlp2_fwd_impl(x, x_div, theta, theta_stride, P, d_in, hidden, n_hidden, off_a, d_out_a, out_a, off_b, d_out_b, out_b,
-                           workspace, stash, B, n, dtype, stream, &tail, &tail_done);
+                           workspace, stash, B, n, dtype, stream, &tail, &tail_done, act);
     } else {
         rc = mlp2_fwd_impl(x, x_div, theta, theta_stride, P, d_in, hidden, n_hidden, off_a, d_out_a, out_a, off_b, d_out_b, out_b,
-                           workspace, stash, B, n, dtype, stream, nullptr, nullptr);
+                           workspace, stash, B, n, dtype, stream, nullptr, nullptr, act);
     }
     if (rc || tail_done) return rc;
     return pacoh_svgd_dist_advance(svgd_X, svgd_workspace, svgd_P, svgd_D, counter, dtype, stream);
+}
+extern "C" int pacoh_mlp2_fwd_svgd(const void* x, int x_div, const void* theta, long theta_stride, int P, int d_in,
+                                   const int32_t* hidden, int n_hidden, long off_a, int d_out_a, void* out_a, long off_b, int d_out_b,
+                                   void* out_b, void* workspace, void* stash, int B, int n,
+                                   const void* svgd_X, void* svgd_workspace, int svgd_P, int svgd_D, int64_t* counter,
+                                   int dtype, void* stream) {
+    return mlp2_fwd_svgd_impl(nullptr, x, x_div, theta, theta_stride, P, d_in, hidden, n_hidden, off_a, d_out_a, out_a, off_b, d_out_b, out_b,
+                              workspace, stash, B, n, svgd_X, svgd_workspace, svgd_P, svgd_D, counter, dtype, stream);
+}
+extern "C" int pacoh_mlp2_fwd_svgd_active(const pacoh_active_tasks* act, const void* x, int x_div, const void* theta, long theta_stride,
+                                          int P, int d_in, const int32_t* hidden, int n_hidden, long off_a, int d_out_a, void* out_a,
+                                          long off_b, int d_out_b, void* out_b, void* workspace, void* stash, int B, int n,
+                                          const void* svgd_X, void* svgd_workspace, int svgd_P, int svgd_D, int64_t* counter,
+                                          int dtype, void* stream) {
+    return mlp2_fwd_svgd_impl(act, x, x_div, theta, theta_stride, P, d_in, hidden, n_hidden, off_a, d_out_a, out_a, off_b, d_out_b, out_b,
+                              workspace, stash, B, n, svgd_X, svgd_workspace, svgd_P, svgd_D, counter, dtype, stream);
 }
 
 extern "C" size_t pacoh_mlp2_bwd_workspace_bytes(int B, int P, int n, int d_in, const int32_t* hidden, int n_hidden, int d_out_a,
@@ -344,15 +369,21 @@ extern "C" int pacoh_mlp2_bwd(const void* x, int x_div, const void* theta, long 
 
 // pacoh_mlp2_bwd + pacoh_hyper_bwd: the whole gradient epilogue of a step.  On the fused fp32 path the hyper-parameter
 // reduction runs in extra workgroups of the slab-reduction launch (one launch less); elsewhere the two calls in sequence.
-extern "C" int pacoh_mlp2_bwd_hyper(const void* x, int x_div, const void* theta, long theta_stride, int P, int d_in,
-                                    const int32_t* hidden, int n_hidden, long off_a, int d_out_a, const void* g_a, long off_b,
-                                    int d_out_b, const void* g_b, void* d_theta, long d_theta_stride, int accumulate,
-                                    void* workspace, const void* stash, int B, int n,
-                                    int T_, int off_ls, int f, int off_os, int off_noise, int off_const, const void* d_ls,
-                                    const void* d_os, const void* d_noise, const void* d_const, const void* lml, void* lik,
-                                    double lik_scale, const int32_t* info, int32_t* fail_flag,
-                                    void* svgd_workspace, int svgd_P, int svgd_D, const pacoh_adam_inline* opt, int dtype, void* stream) {
+static int mlp2_bwd_hyper_impl(const pacoh_active_tasks* act, const void* x, int x_div, const void* theta, long theta_stride, int P, int d_in,
+                               const int32_t* hidden, int n_hidden, long off_a, int d_out_a, const void* g_a, long off_b,
+                               int d_out_b, const void* g_b, void* d_theta, long d_theta_stride, int accumulate,
+                               void* workspace, const void* stash, int B, int n,
+                               int T_, int off_ls, int f, int off_os, int off_noise, int off_const, const void* d_ls,
+                               const void* d_os, const void* d_noise, const void* d_const, const void* lml, void* lik,
+                               double lik_scale, const int32_t* info, int32_t* fail_flag,
+                               void* svgd_workspace, int svgd_P, int svgd_D, const pacoh_adam_inline* opt, int dtype, void* stream) {
     if (svgd_workspace && (svgd_P <= 0 || svgd_D <= 0)) return PACOH_EINVAL;
+    if (act) {                                             // distinct-task step: the fused fp32 kernels and their riding reduction only
+        if (!act->n_act || !act->task_w || T_ != B / (P > 0 ? P : 1)) return PACOH_EINVAL;
+        if (dtype != PACOH_F32 || args_ok(d_in, hidden, n_hidden, d_out_a) || args_ok(d_in, hidden, n_hidden, d_out_b) ||
+            pick_path(dtype, d_in, hidden, n_hidden, d_out_a, (long)B * n) != PATH_FUSED ||
+            pick_path(dtype, d_in, hidden, n_hidden, d_out_b, (long)B * n) != PATH_FUSED) return PACOH_ELIMIT;
+    }
     if (svgd_workspace && svgd_P > 64) return PACOH_ELIMIT;
     if (opt && (!adam_inline_ok(opt, P, lml) || opt->n_seg < 1)) return PACOH_EINVAL;
     if (opt && opt->next) {
@@ -372,7 +403,8 @@ extern "C" int pacoh_mlp2_bwd_hyper(const void* x, int x_div, const void* theta,
                                     ties_scale(f), (const float*)svgd_workspace, svgd_P,
                                     svgd_workspace ? (float*)svgd_workspace + svgd_bw_slot(svgd_P, svgd_D) : nullptr,
                                     opt ? adam_inline_f32(opt) : AdamInline<float>{},
-                                    (opt && opt->next) ? step_next_f32(opt->next, off_ls, f, off_os, off_noise) : StepNextArgs<float>{}};
+                                    (opt && opt->next) ? step_next_f32(opt->next, off_ls, f, off_os, off_noise) : StepNextArgs<float>{},
+                                    act ? act->n_act : nullptr, act ? (const float*)act->task_w : nullptr};
         rc = mlp2_bwd_impl(x, x_div, theta, theta_stride, P, d_in, hidden, n_hidden, off_a, d_out_a, g_a, off_b, d_out_b, g_b, d_theta,
                            d_theta_stride, accumulate, workspace, stash, B, n, dtype, stream, &tail, &tail_done);
     } else {
@@ -384,6 +416,32 @@ extern "C" int pacoh_mlp2_bwd_hyper(const void* x, int x_div, const void* theta,
                          d_theta_stride, lml, lik, lik_scale, info, fail_flag, svgd_workspace, svgd_P, svgd_D, nullptr, dtype, stream);
     if (rc || !opt) return rc;
     return adam_inline_fallback(opt, d_theta, lik, dtype, stream);
+}
+
+extern "C" int pacoh_mlp2_bwd_hyper(const void* x, int x_div, const void* theta, long theta_stride, int P, int d_in,
+                                    const int32_t* hidden, int n_hidden, long off_a, int d_out_a, const void* g_a, long off_b,
+                                    int d_out_b, const void* g_b, void* d_theta, long d_theta_stride, int accumulate,
+                                    void* workspace, const void* stash, int B, int n,
+                                    int T_, int off_ls, int f, int off_os, int off_noise, int off_const, const void* d_ls,
+                                    const void* d_os, const void* d_noise, const void* d_const, const void* lml, void* lik,
+                                    double lik_scale, const int32_t* info, int32_t* fail_flag,
+                                    void* svgd_workspace, int svgd_P, int svgd_D, const pacoh_adam_inline* opt, int dtype, void* stream) {
+    return mlp2_bwd_hyper_impl(nullptr, x, x_div, theta, theta_stride, P, d_in, hidden, n_hidden, off_a, d_out_a, g_a, off_b, d_out_b, g_b,
+                               d_theta, d_theta_stride, accumulate, workspace, stash, B, n, T_, off_ls, f, off_os, off_noise, off_const, d_ls,
+                               d_os, d_noise, d_const, lml, lik, lik_scale, info, fail_flag, svgd_workspace, svgd_P, svgd_D, opt, dtype, stream);
+}
+// ... of a distinct-task step (include/pacoh_gp.h, pacoh_active_tasks)
+extern "C" int pacoh_mlp2_bwd_hyper_active(const pacoh_active_tasks* act, const void* x, int x_div, const void* theta, long theta_stride,
+                                           int P, int d_in, const int32_t* hidden, int n_hidden, long off_a, int d_out_a, const void* g_a,
+                                           long off_b, int d_out_b, const void* g_b, void* d_theta, long d_theta_stride, int accumulate,
+                                           void* workspace, const void* stash, int B, int n,
+                                           int T_, int off_ls, int f, int off_os, int off_noise, int off_const, const void* d_ls,
+                                           const void* d_os, const void* d_noise, const void* d_const, const void* lml, void* lik,
+                                           double lik_scale, const int32_t* info, int32_t* fail_flag,
+                                           void* svgd_workspace, int svgd_P, int svgd_D, const pacoh_adam_inline* opt, int dtype, void* stream) {
+    return mlp2_bwd_hyper_impl(act, x, x_div, theta, theta_stride, P, d_in, hidden, n_hidden, off_a, d_out_a, g_a, off_b, d_out_b, g_b,
+                               d_theta, d_theta_stride, accumulate, workspace, stash, B, n, T_, off_ls, f, off_os, off_noise, off_const, d_ls,
+                               d_os, d_noise, d_const, lml, lik, lik_scale, info, fail_flag, svgd_workspace, svgd_P, svgd_D, opt, dtype, stream);
 }
 
 // pacoh_mlp_bwd + pacoh_hyper_bwd for configurations with ONE network (mean or kernel features): as pacoh_mlp2_bwd_hyper, the

@@ -27,6 +27,7 @@
 #include "common.h"
 #include "hyper_tail.h"
 #include "step_tail.h"
+#include "mlp_fused_split.h"
 #include <stdlib.h>
 
 namespace pacoh {
@@ -73,7 +74,20 @@ struct FusedArgs {
     const float* bw_d2; float* bw_out; int bw_P;
     long* adv_counter;         // backward: the same workgroup advances the pipelined feed's step counter (PACOH-MAP; the slab reduction
                                // behind this launch reads it)
+    const int32_t* n_act;      // distinct-task step: only the rows of the first *n_act tasks are live (nullptr: all R) ...
+    int tiles;                 // ... of the `tiles` tiles the grid was planned for (fused_live_rows)
 };
+
+// The rows R a launch works on and the tiles of tp points each of its workgroups takes: those of the arguments, or -- distinct-task
+// step (mlp_fused_split.h) -- the live rows, dealt out again over the launch's workgroups.  The kernels use these two wherever they
+// used a.R / a.tiles_per_wg; a workgroup left without tiles still writes its (zero) gradient slab.
+__device__ __forceinline__ void fused_live_rows(const FusedArgs& a, int tp, int& R, int& tpw) {
+    R = a.R; tpw = a.tiles_per_wg;
+    if (!a.n_act) return;
+    const int live = *a.n_act * a.n;
+    if (live < R) R = live;
+    tpw = fused_split_tiles((R + tp - 1) / tp, a.tiles, (int)gridDim.x, tpw);
+}
 
 // stash element (particle p, 16-point block blk, slot, feature block fb): 256 floats, lane-major f32x4
 __device__ __forceinline__ long stash_off(const FusedArgs& a, int p, int blk, int slot, int fb, int lane) {
@@ -125,12 +139,12 @@ __device__ void fused_load_weights(float* wl, const float* __restrict__ th, cons
 // as 8-byte fields of 32-byte rows the compiler's ds_read2_b64 pairs were 4-way conflicted).
 // Returns the output row (problem*n + point) of this lane's point, or -1.
 template <int PB, bool BWD>
-__device__ __forceinline__ long stage_tile(const FusedArgs& a, const FusedNet& nt, int p, int row0, float* st, int lane) {
+__device__ __forceinline__ long stage_tile(const FusedArgs& a, const FusedNet& nt, int p, int row0, float* st, int lane, int R) {
     long orow = -1;
     if (lane < 16 * PB) {
         const int row = row0 + lane;
-        const bool valid = row < a.R;
-        const int rr = valid ? row : a.R - 1;
+        const bool valid = row < R;
+        const int rr = valid ? row : R - 1;
         const int t = (int)((unsigned)rr / (unsigned)a.n), i = rr - t * a.n;
         const int bi = t * a.P + p;
         const int xb = a.x_div == 1 ? bi : (int)((unsigned)bi / (unsigned)a.x_div);
@@ -273,10 +287,10 @@ __device__ __forceinline__ void stash_put(const FusedArgs& a, const FusedNet& nt
 // blocks that start past the end of the particle's rows were never written by a forward with a smaller tile: zeros
 template <int PB>
 __device__ __forceinline__ void stash_get(const FusedArgs& a, const FusedNet& nt, int p, int blk0, int slot, int lane,
-                                          f32x4 (&H)[2][PB]) {
+                                          f32x4 (&H)[2][PB], int R) {
 #pragma unroll
     for (int pb = 0; pb < PB; ++pb) {
-        const bool in = (blk0 + pb) * 16 < a.R;
+        const bool in = (blk0 + pb) * 16 < R;
 #pragma unroll
         for (int fb = 0; fb < 2; ++fb)
             H[fb][pb] = in ? stash_ld(reinterpret_cast<const f32x4*>(nt.stash + stash_off(a, p, blk0 + pb, slot, fb, lane)))
@@ -293,6 +307,8 @@ __global__ void __launch_bounds__(256, MINW) mlp_fused_fwd_kernel(FusedArgs a) {
         svgd_dist_tail<float>(a.sv, (int)(blockIdx.y * gridDim.x + blockIdx.x), (int)(gridDim.x * gridDim.y));
         return;
     }
+    int R, tpw;
+    fused_live_rows(a, 16 * PB, R, tpw);
     const FusedNet& nt = a.net[blockIdx.z];
     const int p = blockIdx.y;
     fused_load_weights<NH>(wl, a.theta + (long)p * a.theta_stride + nt.theta_off, a, nt.d_out);
@@ -309,10 +325,10 @@ __global__ void __launch_bounds__(256, MINW) mlp_fused_fwd_kernel(FusedArgs a) {
             for (int s = 0; s < 4; ++s) w3r[o][fb][s] = wo[o * 32 + fb * 16 + 4 * g + s];
     const float b30 = wo[64], b31 = wo[65];
     constexpr int TP = 16 * PB;
-    for (int tl = wave; tl < a.tiles_per_wg; tl += 4) {
-        const int row0 = (blockIdx.x * a.tiles_per_wg + tl) * TP;
-        if (row0 >= a.R) break;
-        const long orow_l = stage_tile<PB, false>(a, nt, p, row0, st, lane);
+    for (int tl = wave; tl < tpw; tl += 4) {
+        const int row0 = (blockIdx.x * tpw + tl) * TP;
+        if (row0 >= R) break;
+        const long orow_l = stage_tile<PB, false>(a, nt, p, row0, st, lane, R);
         f32x4 HA[2][PB], HB[2][PB];
         const int blk0 = row0 >> 4;
         const int ns = nt.stash ? a.n_stash : 0;
@@ -361,6 +377,8 @@ __global__ void __launch_bounds__(256, MINW) mlp_fused_bwd_kernel(FusedArgs a) {
         }
         return;
     }
+    int R, tpw;
+    fused_live_rows(a, 16 * PB, R, tpw);
     float* wl = lds;
     const FusedNet& nt = a.net[blockIdx.z];
     const int p = blockIdx.y;
@@ -381,17 +399,17 @@ __global__ void __launch_bounds__(256, MINW) mlp_fused_bwd_kernel(FusedArgs a) {
     float aBoT[2] = {};
 
     constexpr int TP = 16 * PB;
-    for (int tl = wave; tl < a.tiles_per_wg; tl += 4) {
-        const int row0 = (blockIdx.x * a.tiles_per_wg + tl) * TP;
-        if (row0 >= a.R) break;
-        stage_tile<PB, true>(a, nt, p, row0, st, lane);
+    for (int tl = wave; tl < tpw; tl += 4) {
+        const int row0 = (blockIdx.x * tpw + tl) * TP;
+        if (row0 >= R) break;
+        stage_tile<PB, true>(a, nt, p, row0, st, lane, R);
         // ---- activations: the top `ns` hidden layers from the forward's stash, the ones below recomputed -------------
         f32x4 H[NH][2][PB];
         const int blk0 = row0 >> 4;
         const int ns = nt.stash ? a.n_stash : 0;
 #pragma unroll
         for (int l = NH - 1; l >= 0; --l)
-            if (l >= NH - ns) stash_get<PB>(a, nt, p, blk0, l - (NH - ns), lane, H[l]);
+            if (l >= NH - ns) stash_get<PB>(a, nt, p, blk0, l - (NH - ns), lane, H[l], R);
         if (ns < NH) f_layer1<PB>(wl, st, r, g, H[0]);
 #pragma unroll
         for (int l = 1; l < NH; ++l)
@@ -625,6 +643,20 @@ static void fused_fill(FusedArgs& a, const void* x, int x_div, const void* theta
     for (int k = 0; k < 2; ++k) a.net[k].stash = (a.n_stash > 0 && k < nets) ? (float*)stash + k * per_net : nullptr;
 }
 
+// forward: tiles per workgroup (a wave takes every 4th): 16 at cfg #3 (4 / 8 / 16 / 32: 109 / 100 / 95 / 94 us); small batches -- the 1/8
+// strong-scaling shard -- want fewer, or a SIMD holds two four-tile waves while its neighbour idles: the count that minimises
+// (waves per SIMD) x (tiles per wave + half a tile of fixed cost), larger counts winning ties
+static int fused_fwd_tpw(int tiles, int P, int nets) {
+    int pick = 4;
+    double best = 1e30;
+    for (int tpw = 4; tpw <= 32; tpw *= 2) {
+        const long waves = (long)((tiles + tpw - 1) / tpw) * P * nets * 4;
+        const double cost = (double)((waves + 1023) / 1024) * (tpw / 4 + 0.5);
+        if (cost <= best * 1.02 || tpw == 4) { if (cost < best) best = cost; pick = tpw; }
+    }
+    return pick;
+}
+
 constexpr int BWD_MINW = 3;      // NH <= 2, 64-point tiles: three waves per SIMD (168 registers; forcing 128 spills)
 constexpr int BWD_MINW_PB2 = 2;
 // M is applied to the parenthesised kernel instantiation (the commas of the template arguments must not split macro arguments)
@@ -642,21 +674,14 @@ constexpr int BWD_MINW_PB2 = 2;
 // nets = 1 or 2 networks of the SAME hidden shape at element offsets off[k] of the theta rows
 int mlp_fused_fwd(const void* x, int x_div, const void* theta, long theta_stride, int P, int d_in, const int32_t* hidden,
                   int n_hidden, int nets, const long* off, const int* d_out, void* const* out, void* stash, int B, int n,
-                  hipStream_t s, const SvgdDistTail<float>* tail, bool* tail_taken) {
+                  hipStream_t s, const SvgdDistTail<float>* tail, bool* tail_taken, const int32_t* n_act) {
     FusedArgs a = {};
     fused_fill(a, x, x_div, theta, theta_stride, P, d_in, hidden, n_hidden, B, n, stash, nets);
     for (int k = 0; k < nets; ++k) { a.net[k].theta_off = off[k]; a.net[k].out = (float*)out[k]; a.net[k].d_out = d_out[k]; }
     const int pb = fused_fwd_pb(a.R, P, nets);
     const int tiles = (a.R + 16 * pb - 1) / (16 * pb);
-    // tiles per workgroup (a wave takes every 4th): 16 at cfg #3 (4 / 8 / 16 / 32: 109 / 100 / 95 / 94 us); small batches -- the 1/8
-    // strong-scaling shard -- want fewer, or a SIMD holds two four-tile waves while its neighbour idles: the count that minimises
-    // (waves per SIMD) x (tiles per wave + half a tile of fixed cost), larger counts winning ties
-    double best = 1e30;
-    for (int tpw = 4; tpw <= 32; tpw *= 2) {
-        const long waves = (long)((tiles + tpw - 1) / tpw) * P * nets * 4;
-        const double cost = (double)((waves + 1023) / 1024) * (tpw / 4 + 0.5);
-        if (cost <= best * 1.02 || tpw == 4) { if (cost < best) best = cost; a.tiles_per_wg = tpw; }
-    }
+    a.n_act = n_act; a.tiles = tiles;
+    a.tiles_per_wg = fused_fwd_tpw(tiles, P, nets);
     const int wgs = (tiles + a.tiles_per_wg - 1) / a.tiles_per_wg;
     // The tail slice of the grid has wgs x P workgroups for the P (P + 1) / 2 particle pairs (+ the snapshot rows).  A thin slice walks
     // several pairs per workgroup one after the other, each a dependent chain of loads and a barrier: at the reference launcher's shape
@@ -679,15 +704,20 @@ int mlp_fused_fwd(const void* x, int x_div, const void* theta, long theta_stride
 
 struct FusedBwdPlan { int pb, chunks, tiles_per_wg; };
 
-static FusedBwdPlan fused_bwd_plan(int R, int P, int nets, int n_hidden) {
+// resident_given > 0: plan for that many resident workgroups instead of asking the device (pacoh_mlp_fused_plan: host-side tests)
+static FusedBwdPlan fused_bwd_plan(int R, int P, int nets, int n_hidden, int resident_given = 0) {
     FusedBwdPlan pl;
     pl.pb = fused_bwd_pb(n_hidden, R, P, nets);
     static int resident[FMAXNH + 1][2] = {};
-    int& res = resident[n_hidden][pl.pb == 4];
-    if (res == 0) {
-#define PACOH_OCC(K) res = resident_wgs(K)
-        PACOH_FUSED_DISPATCH(mlp_fused_bwd_kernel, n_hidden, pl.pb, PACOH_OCC);
+    int res = resident_given;
+    if (res <= 0) {
+        int& cached = resident[n_hidden][pl.pb == 4];
+        if (cached == 0) {
+#define PACOH_OCC(K) cached = resident_wgs(K)
+            PACOH_FUSED_DISPATCH(mlp_fused_bwd_kernel, n_hidden, pl.pb, PACOH_OCC);
 #undef PACOH_OCC
+        }
+        res = cached;
     }
     const int tp = 16 * pl.pb;
     pl.chunks = fused_chunks(R, P, nets, tp, res, 0.4 * 64 / tp);
@@ -710,6 +740,7 @@ int mlp_fused_bwd(const void* x, int x_div, const void* theta, long theta_stride
     fused_fill(a, x, x_div, theta, theta_stride, P, d_in, hidden, n_hidden, B, n, stash, nets);
     const FusedBwdPlan pl = fused_bwd_plan(a.R, P, nets, n_hidden);
     a.tiles_per_wg = pl.tiles_per_wg;
+    a.n_act = tail ? tail->n_act : nullptr; a.tiles = (a.R + 16 * pl.pb - 1) / (16 * pl.pb);
     float* ws = (float*)workspace;
     SlabReduce sr[2] = {};
     int wmax = 0;
@@ -740,6 +771,29 @@ int mlp_fused_bwd(const void* x, int x_div, const void* theta, long theta_stride
                        rtail, tail_blocks, (float*)nullptr, (const int*)nullptr);
     return launch_status();
 }
+
+}  // namespace pacoh
+
+// (include/pacoh_gp.h) the split and the host plans it starts from, for tests
+extern "C" int pacoh_mlp_fused_split(int tiles_eff, int tiles_full, int wgs, int tpw_host) {
+    return pacoh::fused_split_tiles(tiles_eff, tiles_full, wgs, tpw_host);
+}
+extern "C" int pacoh_mlp_fused_plan(int R, int P, int nets, int n_hidden, int bwd, int resident, int* tile_points, int* wgs, int* tiles_per_wg) {
+    using namespace pacoh;
+    if (R <= 0 || P <= 0 || nets < 1 || nets > 2 || n_hidden < 1 || n_hidden > FMAXNH || !tile_points || !wgs || !tiles_per_wg) return PACOH_EINVAL;
+    if (bwd) {
+        const FusedBwdPlan pl = fused_bwd_plan(R, P, nets, n_hidden, resident);
+        *tile_points = 16 * pl.pb; *wgs = pl.chunks; *tiles_per_wg = pl.tiles_per_wg;
+    } else {
+        const int pb = fused_fwd_pb(R, P, nets);
+        *tile_points = 16 * pb;
+        *tiles_per_wg = fused_fwd_tpw((R + 16 * pb - 1) / (16 * pb), P, nets);
+        *wgs = ((R + 16 * pb - 1) / (16 * pb) + *tiles_per_wg - 1) / *tiles_per_wg;
+    }
+    return PACOH_OK;
+}
+
+namespace pacoh {
 
 // The slab reduction as a launch of its own: the task-fused PACOH-MAP kernel (map_task.hip) writes one slab per workgroup and
 // network in theta's layout; this sums them into d_theta and runs the step's tail (hyper-parameter reduction, AdamW, next batch).

@@ -10,6 +10,8 @@
 // pacoh_step_begin on row 0, then c := -1) leaves row 0 gathered and its scalars in sc2[0]; the forward's tail does c += 1 (nothing
 // else in that launch reads c); the update reads its scalars from sc2[c & 1] while its tail writes row c + 1's into sc2[(c + 1) & 1]
 // and gathers row c + 1's tasks into the batch buffers, which no other workgroup of the update reads.
+// Distinct-task feed (StepNextArgs::nact_all): the row's count of distinct tasks and their multiplicities travel the same way, into
+// the fixed buffers o_nact / o_mult, which the forward, GP and backward launches of the NEXT step read and the update does not.
 #pragma once
 #include "common.h"
 
@@ -177,6 +179,9 @@ struct StepNextArgs {
     T* ox; T* oy; int32_t* onv; int nx, ny;          // the batch buffers of the next step
     int off_ls, f, off_os, off_noise, tie; T noise_floor; T* ls; T* os; T* noise;      // hyper-parameters of the UPDATED particles
     const T* bw_pre;                                 // the step's bandwidth, computed ahead (svgd_bandwidth_block) | nullptr
+    // distinct-task feed (nullptr: every draw is evaluated): the chunk's rows hold each draw's DISTINCT tasks first, nact_all[rows] how
+    // many they are and mult_all[rows, tb] how often each was drawn; the gatherer publishes the next row's values in o_nact / o_mult
+    const int32_t* nact_all; const T* mult_all; int32_t* o_nact; T* o_mult;
 };
 
 template <typename T>
@@ -192,9 +197,11 @@ __device__ __forceinline__ void step_next_tail(const StepNextArgs<T>& a, int lin
             for (int q = threadIdx.x; q < a.nx; q += 256) dx[q] = sx[q];
             for (int q = threadIdx.x; q < a.ny; q += 256) dy[q] = sy[q];
             if (threadIdx.x == 0 && a.n_valid) a.onv[blk] = a.n_valid[t];
+            if (threadIdx.x == 0 && a.nact_all) a.o_mult[blk] = a.mult_all[row * a.tb + blk];
         } else {
             T* dst = a.sc2 + (row & 1) * a.n_sc;
             for (int q = threadIdx.x; q < a.n_sc; q += 256) dst[q] = a.sc_all[row * a.n_sc + q];
+            if (threadIdx.x == 0 && a.nact_all) *a.o_nact = a.nact_all[row];
         }
     }
 }

@@ -151,14 +151,47 @@ class AsyncUploader:
         return out
 
 
+def distinct_rows(idx, dtype=np.float32):
+    """Each row of the task draws idx [k, tb] (with replacement) as its DISTINCT tasks: -> (rows [k, tb] int64: the row's distinct
+    ids in order of first occurrence, padded with its first id; mult [k, tb]: how often each was drawn, 0 for the padding;
+    n_act [k] int32: how many they are).  sum_{draws t} g(t) = sum_{j < n_act} mult[j] g(rows[j]).  A row without repeats comes back
+    as it is, with all counts 1 and n_act == tb.  Vectorised over the rows: a chunk is up to 1024 rows of 1024 draws."""
+    idx = np.ascontiguousarray(idx, dtype=np.int64)
+    k, tb = idx.shape
+    # equal ids side by side, earlier draws first (a stable sort; 16-bit keys take numpy's radix sort: 5x faster on a full chunk)
+    keys = idx.astype(np.int16) if tb > 0 and 0 <= idx.min() and idx.max() < 2 ** 15 else idx
+    order = np.argsort(keys, axis=1, kind='stable')
+    srt = np.take_along_axis(keys, order, axis=1)
+    head = np.ones((k, tb), dtype=bool)                               # first draw of its id, in the sorted row
+    head[:, 1:] = srt[:, 1:] != srt[:, :-1]
+    run = np.cumsum(head, axis=1) - 1                                 # number of the id's run in the sorted row
+    counts = np.bincount((run + np.arange(k)[:, None] * tb).ravel(), minlength=k * tb).reshape(k, tb)      # length of run j
+    first = np.zeros((k, tb), dtype=bool)                             # ... in the row as drawn
+    np.put_along_axis(first, order, head, axis=1)
+    cnt_at = np.empty((k, tb), dtype=np.int64)                        # how often the id at a draw position was drawn
+    np.put_along_axis(cnt_at, order, np.take_along_axis(counts, run, axis=1), axis=1)
+    n_act = first.sum(axis=1).astype(np.int32)
+    slot = np.cumsum(first, axis=1) - 1                               # first occurrences keep their order
+    r, c = np.nonzero(first)
+    rows = np.repeat(idx[:, :1], tb, axis=1)                          # (padding: the row's first id)
+    mult = np.zeros((k, tb), dtype=dtype)
+    rows[r, slot[r, c]] = idx[r, c]
+    mult[r, slot[r, c]] = cnt_at[r, c]
+    return rows, mult, n_act
+
+
 class StepFeed:
     """Per-step operands of a graph-captured meta-training step (include/pacoh_gp.h, "whole steps as hipGraphs"): the task draws
     of up to `chunk` steps idx_all[chunk, tb], their step scalars sc_all[chunk, SC_COUNT] and an optional per-step payload
     aux_all[chunk, ...] (PACOH-VI: the reparameterisation noise) are uploaded with one copy each from pinned memory; select() --
     the first launch of the captured step -- moves the current row into the fixed buffers idx / sc / aux the kernels read and
-    advances the device-side counter."""
+    advances the device-side counter.
+    dedup (set by the learner before the first upload; PACOH-SVGD on the throughput kernels): upload() rewrites every row of task
+    draws as its distinct tasks (distinct_rows) with mult_all[chunk, tb] / nact_all[chunk] beside idx_all; whoever gathers a row's
+    tasks publishes its entries in the fixed buffers mult [tb] / nact [1] the step's kernels read (active())."""
 
     _warned_threads = False
+    dedup = False
 
     def __init__(self, device, dtype, tb, chunk=1024, aux_shape=None):
         if not StepFeed._warned_threads:
@@ -195,6 +228,25 @@ class StepFeed:
         self._n_idx = [t.numpy() for t in self._h_idx]
         self._n_sc = [t.numpy() for t in self._h_sc]
         self._n_aux = [t.numpy() for t in self._h_aux] if self._h_aux is not None else None
+        self.mult_all = self.nact_all = self.mult = self.nact = None
+
+    def enable_dedup(self):
+        """evaluate every distinct task of a step's draw once (before the first upload)"""
+        assert self.tb > 0 and self._ev[0] is None and self._ev[1] is None
+        rows = self.idx_all.shape[0]
+        self.dedup = True
+        self.mult_all = torch.ones(rows, self.tb, dtype=self.dtype, device=self.device)
+        self.nact_all = torch.full((rows,), self.tb, dtype=torch.int32, device=self.device)
+        self.mult = torch.ones(self.tb, dtype=self.dtype, device=self.device)
+        self.nact = torch.full((1,), self.tb, dtype=torch.int32, device=self.device)
+        self._h_mult = [torch.zeros(rows, self.tb, dtype=self.dtype).pin_memory() for _ in range(2)]
+        self._h_nact = [torch.zeros(rows, dtype=torch.int32).pin_memory() for _ in range(2)]
+        self._n_mult = [t.numpy() for t in self._h_mult]
+        self._n_nact = [t.numpy() for t in self._h_nact]
+
+    def active(self):
+        """(nact, mult) for the kernels of a step (GPEngine.lml_and_grad(active=...)), or None"""
+        return (self.nact, self.mult) if self.dedup else None
 
     def upload(self, idx_rows, sc_rows, aux_rows=None):
         """idx_rows: int array [k, tb]; sc_rows: k rows of L.step_scalars(); aux_rows: tensor [k, ...], k tensors [...], a callable
@@ -217,7 +269,14 @@ class StepFeed:
         self.sc_all[:kk].copy_(self._h_sc[q][:kk], non_blocking=True)
         if self.tb > 0:
             hi = self._n_idx[q]
-            hi[:k] = np.asarray(idx_rows).reshape(k, self.tb)
+            if self.dedup:
+                hi[:k], hm, hn = distinct_rows(np.asarray(idx_rows).reshape(k, self.tb), self._n_mult[q].dtype)
+                self._n_mult[q][:k], self._n_nact[q][:k] = hm, hn
+                self._n_mult[q][k:kk], self._n_nact[q][k:kk] = hm[k - 1], hn[k - 1]
+                self.mult_all[:kk].copy_(self._h_mult[q][:kk], non_blocking=True)
+                self.nact_all[:kk].copy_(self._h_nact[q][:kk], non_blocking=True)
+            else:
+                hi[:k] = np.asarray(idx_rows).reshape(k, self.tb)
             hi[k:kk] = hi[k - 1]
             self.idx_all[:kk].copy_(self._h_idx[q][:kk], non_blocking=True)
         if self.aux_all is not None:
@@ -663,7 +722,7 @@ class GPEngine:
             return lay.block_range('mean_nn.')[0], lay.block_range('kernel_nn.')[0]
         return None
 
-    def _features(self, theta, x, T, n, theta_per_task=False, keep=False, svgd_tail=None):
+    def _features(self, theta, x, T, n, theta_per_task=False, keep=False, svgd_tail=None, active=None):
         """kernel inputs z (+ divisor) and mean (+ mode) for B = T*P problems (b = t*P + p: task t, parameter row p).
         theta_per_task: theta holds T*S rows, S of its own per task -- the same kernels with P = T*S parameter rows, ONE
         problem per row (B = T*S) and inputs shared by S consecutive problems.  keep: park the activations the backward of the
@@ -680,8 +739,9 @@ class GPEngine:
                                                      self._ws.get(key))
             mean, z = L.mlp2_fwd(x, x_div, theta, P, lay.input_dim, list(lay.mean_nn_layers), pair[0], 1, pair[1],
                                  lay.feature_dim, B, n, ws_holder=self._ws, stash=stash,
-                                 svgd_tail=svgd_tail[:3] if svgd_tail is not None else None)
+                                 svgd_tail=svgd_tail[:3] if svgd_tail is not None else None, active=active)
             return z, 1, mean.reshape(B, n), L.MEAN_VECTOR
+        assert active is None, 'distinct-task steps run on the paired fused networks only'
         if svgd_tail is not None:
             L.svgd_dist_advance(*svgd_tail[:3])            # (no paired forward launch to ride in)
         one_net = (lay.covar_module == 'NN') != (lay.mean_module == 'NN')      # the backward of ONE network can read a stash too
@@ -724,7 +784,7 @@ class GPEngine:
         return lml.reshape(T, P), info
 
     def lml_and_grad(self, theta, batch, weight=1.0, lik_out=None, lik_scale=1.0, grad_out=None, fail_flag=None, hypers=None,
-                     svgd_tail=None, opt=None):
+                     svgd_tail=None, opt=None, active=None):
         """returns (lml[T,P], grad[P,D]) with grad = d(weight * sum_t lml[t,p]) / d theta[p];
         lik_out[P] (optional) receives lik_scale * sum_t lml[t,p] from the same launch that reduces the hyper-gradients;
         grad_out[P,D] (optional, contiguous) is used for the gradient instead of a fresh tensor;
@@ -732,14 +792,18 @@ class GPEngine:
         svgd_tail = (particles, workspace, counter, want_bandwidth): the pipelined SVGD step's distance matrix and counter
         increment, in extra workgroups of the forward launch where there is one (L.mlp2_fwd), and -- want_bandwidth -- its median
         bandwidth by one more workgroup of the hyper-parameter reduction (L.hyper_bwd);
-        opt (L.adam_inline(...), one parameter row): the AdamW step is applied to every gradient entry where it is finished"""
+        opt (L.adam_inline(...), one parameter row): the AdamW step is applied to every gradient entry where it is finished;
+        active = (n_act int32 [1], task_w [T]) in device memory (StepFeed.active()): the batch holds the DISTINCT tasks of a draw
+        with replacement in its first n_act slots and task_w their multiplicities -- only those are evaluated, each counting
+        task_w times: grad = d(weight * sum_t task_w[t] lml[t,p]) / d theta[p]; the rows of the returned lml behind n_act are
+        undefined.  fp32, paired fused networks, n <= 128, f <= 4 only."""
         lay = self.layout
         P, D = theta.shape
         T, n = batch.T, batch.n
         B = T * P
         dev, dt = theta.device, theta.dtype
         ls, os_, noise = hypers if hypers is not None else self._hypers(theta)      # (hypers: already transformed by pacoh_step_begin)
-        z, z_div, mean, mode = self._features(theta, batch.x, T, n, keep=True, svgd_tail=svgd_tail)
+        z, z_div, mean, mode = self._features(theta, batch.x, T, n, keep=True, svgd_tail=svgd_tail, active=active)
         g = None                                        # weight 1: the kernels take g_lml = NULL
         if float(weight) != 1.0:
             gkey = ('g', B, dt, dev)                    # ONE upstream-gradient vector per batch shape, refilled when the weight changes
@@ -751,7 +815,8 @@ class GPEngine:
             g = ent[0]
         lml, d_z, d_mean, d_ls, d_os, d_noise, info = L.gp_lml_fwdbwd(
             z, z_div, mean, mode, batch.y, P, ls, os_, noise, B, P,
-            n_valid=batch.n_valid if batch.ragged else None, g_lml=g, want_dz=(lay.covar_module == 'NN'), kernel=lay.kernel_code)
+            n_valid=batch.n_valid if batch.ragged else None, g_lml=g, want_dz=(lay.covar_module == 'NN'), kernel=lay.kernel_code,
+            active=active)
         grad = grad_out if grad_out is not None else torch.empty(P, D, dtype=dt, device=dev)   # every block is written below
         pair = self._paired_nets()
         off_ls, f, off_os, off_noise, off_c = self._hyper_offsets()
@@ -767,8 +832,9 @@ class GPEngine:
             self._ws['mk'] = L.mlp2_bwd_hyper(batch.x, P, theta, P, lay.input_dim, list(lay.mean_nn_layers), pair[0], 1,
                                               d_mean.reshape(B, n, 1), pair[1], lay.feature_dim, d_z, grad, B, n, T, off_ls, f, off_os,
                                               off_noise, off_c, d_ls, d_os, d_noise, None, workspace=self._ws.get('mk'),
-                                              stash=self._ws.get(('stash', B, n)), **hyper)
+                                              stash=self._ws.get(('stash', B, n)), active=active, **hyper)
             return lml.reshape(T, P), grad, info
+        assert active is None
         d_const = d_mean if lay.mean_module == 'constant' else None
         if (lay.covar_module == 'NN') != (lay.mean_module == 'NN'):
             # ONE network: its backward and the hyper-parameter reduction in one call (one launch less on the fused path)
