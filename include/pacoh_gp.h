@@ -165,6 +165,53 @@ int pacoh_gp_loo(const void* z, int z_div, const void* mean, int mean_mode, cons
                  void* mu_loo, void* var_loo, void* lpd, int32_t* info,
                  int B, int P, int n, int f, int dtype, void* stream);
 
+/* ---- conditioned GP posterior: condition once, predict many times, append points (csrc/gp_cond.hip) ----------------------------
+ * Upstream counterpart: gpytorch's prediction-strategy cache (DefaultPredictionStrategy.mean_cache / covar_cache) and
+ * ExactGP.get_fantasy_model, which the reference's ExactGP sits on; the reference itself never reuses them (every predict() call
+ * rebuilds and refactors the Gram matrix).
+ * STATE of B conditioned problems (b = t*P + p), caller-allocated, capacity `cap` points each, n <= cap of them in use:
+ *   zs[B,cap,f]     context features divided by the problem's lengthscales
+ *   resid[B,cap]    y - mean
+ *   X[B,cap,cap]    row-major; row i < n holds row i of L^-1, where K + j I = L L^T, K = os*k(Z,Z) + noise*I and j is the jitter of the
+ *                   ladder rung in info[b].  The caller zero-fills X once; no kernel ever writes an entry above the diagonal or a
+ *                   row >= n.
+ *   alpha[B,cap]    (K + j I)^-1 resid
+ *   info[B]         the jitter rung 0..3, or -1, exactly as pacoh_gp_lml_fwd reports it
+ * Conventions as pacoh_gp_loo: z_div / y_div sharing, mean modes, kernel family in the bits above `f`, outputscale NULL = 1,
+ * f <= 16, normalised space, error codes; every limit is checked before anything is enqueued.  One size limit:
+ * 1 <= n <= cap <= pacoh_gp_cond_max_n(dtype) = pacoh_gp_loo_max_n(dtype), else PACOH_ELIMIT; there is no large-context path, no
+ * ragged n_valid, no joint covariance and no gradient.
+ *
+ * pacoh_gp_condition: inputs as pacoh_gp_loo with n_valid = NULL.  One fused launch: Gram in LDS, Cholesky with the jitter ladder,
+ *   L^-1 in place, alpha = X^T (X resid); then the state is written.  info[b] = -1: alpha[b,:n] is NaN and the rows of X[b] are
+ *   untouched.
+ * pacoh_gp_cond_predict: for the m >= 1 test points z_tst[B/zt_div,m,f] (mean_tst follows mean_mode; vector: [B,m]), with
+ *   k*_si = os*k(z*_s, z_i):
+ *     mu[b,s]  = mean_tst + sum_i k*_si alpha_i
+ *     var[b,s] = os + noise - |X k*_s|^2        (observation noise included; a jitter rung sits in the factor only, exactly as
+ *                                                pacoh_gp_predict does)
+ *   info[b] < 0: NaN.  var may be NULL.  The grid covers problems x tiles of 64 test points; V = K* X^T runs on the matrix cores.
+ * pacoh_gp_cond_append: appends the k >= 1 points z_new[B/zn_div,k,f], y_new[B/yn_div,k] (mean_new per mode; vector: [B,k]) to
+ *   every problem, n + k <= cap, in order, in one launch (one workgroup per problem).  For the point that becomes index q:
+ *     kappa = os + noise + j,  k_i = os*k(z_q, z_i),  v = X k,  s^2 = kappa - |v|^2,
+ *     X[q,:q] = -(v^T X) / s,  X[q,q] = 1 / s,  u = X[q,:q+1] . resid[:q+1],  alpha[:q+1] += X[q,:q+1] u
+ *   -- O(n^2) per point instead of the O(n^3) refit.  If !(s^2 > 0) for a problem: fail[b] = 1 (int32 [B], zeroed by the caller),
+ *   the problem is not updated further and its state rows < n stay exactly as they were (rows >= n are then undefined; condition
+ *   again on all points).  Problems with info[b] < 0 are skipped.  The caller's n becomes n + k. */
+int pacoh_gp_cond_max_n(int dtype);
+int pacoh_gp_condition(const void* z, int z_div, const void* mean, int mean_mode, const void* y, int y_div,
+                       const void* lengthscale, const void* outputscale, const void* noise,
+                       void* zs, void* resid, void* X, void* alpha, int32_t* info,
+                       int B, int P, int n, int cap, int f, int dtype, void* stream);
+int pacoh_gp_cond_predict(const void* zs, const void* X, const void* alpha, const int32_t* info,
+                          const void* z_tst, int zt_div, const void* mean_tst, int mean_mode,
+                          const void* lengthscale, const void* outputscale, const void* noise, void* mu, void* var,
+                          int B, int P, int n, int cap, int m, int f, int dtype, void* stream);
+int pacoh_gp_cond_append(void* zs, void* resid, void* X, void* alpha, const int32_t* info,
+                         const void* z_new, int zn_div, const void* mean_new, int mean_mode, const void* y_new, int yn_div,
+                         const void* lengthscale, const void* outputscale, const void* noise, int32_t* fail,
+                         int B, int P, int n, int cap, int k, int f, int dtype, void* stream);
+
 /* ---- dense path (large n): Cholesky-based Gaussian log-density of materialised covariances -----
  * logp[b] = log N(resid[b]; 0, A[b]) * scale,  A[B,n,n] symmetric (lower triangle read), destroyed
  * (overwritten by its Cholesky factor).  With A from pacoh_gram_rbf_ard(..., add_noise_diag=1) and

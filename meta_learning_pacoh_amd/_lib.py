@@ -38,6 +38,11 @@ SIGNATURES = {
     'pacoh_gp_lml_fwd': (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'pacoh_gp_loo_max_n': (_i, [_i]),
     'pacoh_gp_loo': (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'pacoh_gp_cond_max_n': (_i, [_i]),
+    'pacoh_gp_condition': (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'pacoh_gp_cond_predict': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'pacoh_gp_cond_append': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp,
+                                  _i, _i, _i, _i, _i, _i, _i, _vp]),
     'pacoh_gp_lml_fwdbwd': (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                  _i, _i, _i, _i, _i, _vp]),
     'pacoh_gp_predict_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
@@ -418,6 +423,141 @@ def gp_loo(z, z_div, mean, mean_mode, y, y_div, lengthscale, outputscale, noise,
                                 _ptr(noise, z), _ptr(n_valid), _ptr(mu), _ptr(var), _ptr(lpd), _ptr(info), B, P, n, _kf(f, kernel),
                                 dtype_code(z), _stream()), 'pacoh_gp_loo')
     return mu, var, lpd, info
+
+
+def gp_cond_max_n(dtype):
+    """largest capacity of a conditioned GP state (= gp_loo_max_n: one LDS-resident matrix per problem at condition time)"""
+    return load_library().pacoh_gp_cond_max_n(F32 if dtype == torch.float32 else F64)
+
+
+def _cond_hypers(lengthscale, outputscale, noise, P):
+    if lengthscale.dim() != 2 or lengthscale.shape[0] != P or noise.numel() != P or (outputscale is not None and outputscale.numel() != P):
+        raise ValueError('lengthscale must be [%d,f], noise and outputscale [%d]' % (P, P))
+
+
+def _cond_mean(mean, mean_mode, B, P, cols):
+    if mean_mode == MEAN_VECTOR:
+        if mean is None or mean.numel() != B * cols:
+            raise ValueError('mean must be [%d,%d] for MEAN_VECTOR' % (B, cols))
+    elif mean_mode == MEAN_CONST:
+        if mean is None or mean.numel() != P:
+            raise ValueError('mean must be [%d] for MEAN_CONST' % P)
+    elif mean_mode != MEAN_ZERO:
+        raise ValueError('unknown mean_mode %r' % (mean_mode,))
+
+
+def _cond_limits(n, cap, dt, k=0):
+    limit = gp_cond_max_n(dt)
+    if cap > limit or n > limit:
+        raise RuntimeError('a conditioned GP keeps the context in LDS at condition time: n = %d, capacity = %d is beyond the limit of %d '
+                           'points for %s (there is no large-context path)' % (n, cap, limit, dt))
+    if n < 1 or n + k > cap:
+        raise RuntimeError('%d points do not fit the capacity of %d (limit of %d points for %s)' % (n + k, cap, limit, dt))
+
+
+def _cond_state(state, B, P):
+    """shapes of the state tuple (zs [B,cap,f], resid [B,cap], X [B,cap,cap], alpha [B,cap], info int32 [B]) -> cap, f"""
+    zs, resid, X, alpha, info = state
+    if zs.dim() != 3 or zs.shape[0] != B:
+        raise ValueError('zs must be [%d,cap,f], got %s' % (B, tuple(zs.shape)))
+    cap, f = zs.shape[1], zs.shape[2]
+    if tuple(resid.shape) != (B, cap) or tuple(alpha.shape) != (B, cap) or tuple(X.shape) != (B, cap, cap):
+        raise ValueError('resid / alpha must be [%d,%d] and X [%d,%d,%d]' % (B, cap, B, cap, cap))
+    if info.dtype != torch.int32 or info.numel() != B:
+        raise ValueError('info must be int32 [%d]' % B)
+    if B <= 0 or P <= 0 or B % P:
+        raise ValueError('B must be a positive multiple of P, got B = %d, P = %d' % (B, P))
+    return cap, f
+
+
+def gp_cond_alloc(B, cap, f, dtype, device):
+    """a zero-filled state (zs, resid, X, alpha, info) of B problems with capacity cap"""
+    z = lambda *s: torch.zeros(*s, dtype=dtype, device=device)
+    return z(B, cap, f), z(B, cap), z(B, cap, cap), z(B, cap), torch.zeros(B, dtype=torch.int32, device=device)
+
+
+def gp_condition(z, z_div, mean, mean_mode, y, y_div, lengthscale, outputscale, noise, B, P, capacity=None, state=None,
+                 kernel=KERNEL_RBF):
+    """condition B = T*P GP problems on their n context points in one launch and keep what a later prediction needs
+    -> state = (zs [B,cap,f], resid [B,cap], X [B,cap,cap] rows of L^-1, alpha [B,cap], info [B]); arguments as gp_loo.  state:
+    buffers to (re)use, X zero above the diagonal; capacity (None: the size limit) is that of a fresh state."""
+    lib = load_library()
+    if z.dim() != 3 or z.shape[0] * z_div < B:
+        raise ValueError('z must be [>= %d,n,f] for z_div %d, got %s' % (-(-B // max(1, z_div)), z_div, tuple(z.shape)))
+    n, f = z.shape[-2], z.shape[-1]
+    dev, dt = z.device, z.dtype
+    if y.dim() != 2 or y.shape[1] != n or y.shape[0] * y_div < B:
+        raise ValueError('y must be [>= %d,%d] for y_div %d, got %s' % (-(-B // max(1, y_div)), n, y_div, tuple(y.shape)))
+    if B <= 0 or P <= 0 or B % P:
+        raise ValueError('B must be a positive multiple of P, got B = %d, P = %d' % (B, P))
+    _cond_hypers(lengthscale, outputscale, noise, P)
+    if lengthscale.shape[1] != f:
+        raise ValueError('lengthscale must be [%d,%d], noise and outputscale [%d]' % (P, f, P))
+    _cond_mean(mean, mean_mode, B, P, n)
+    if state is not None:
+        cap, sf = _cond_state(state, B, P)
+        if sf != f:
+            raise ValueError('the state holds %d features, z has %d' % (sf, f))
+    else:
+        cap = gp_cond_max_n(dt) if capacity is None else int(capacity)
+    _cond_limits(n, cap, dt)
+    if state is None:
+        state = gp_cond_alloc(B, cap, f, dt, dev)
+    zs, resid, X, alpha, info = state
+    with _Timed('gp_condition'):
+        _check(lib.pacoh_gp_condition(_ptr(z), z_div, _ptr(mean, z), mean_mode, _ptr(y, z), y_div, _ptr(lengthscale, z),
+                                      _ptr(outputscale, z), _ptr(noise, z), _ptr(zs, z), _ptr(resid, z), _ptr(X, z), _ptr(alpha, z),
+                                      _ptr(info), B, P, n, cap, _kf(f, kernel), dtype_code(z), _stream()), 'pacoh_gp_condition')
+    return state
+
+
+def gp_cond_predict(state, n, z_tst, zt_div, mean_tst, mean_mode, lengthscale, outputscale, noise, B, P, want_var=True,
+                    kernel=KERNEL_RBF):
+    """posterior predictive of the conditioned problems at z_tst [B / zt_div, m, f] -> mu [B,m], var [B,m] | None (observation noise
+    included; info < 0: NaN).  No factorisation: mu = mean + K* alpha, var = os + noise - |X k*|^2 on the matrix cores."""
+    lib = load_library()
+    cap, f = _cond_state(state, B, P)
+    zs, resid, X, alpha, info = state
+    dev, dt = zs.device, zs.dtype
+    if z_tst.dim() != 3 or z_tst.shape[2] != f or z_tst.shape[0] * zt_div < B or z_tst.shape[1] < 1:
+        raise ValueError('z_tst must be [>= %d,m,%d] for zt_div %d, got %s' % (-(-B // max(1, zt_div)), f, zt_div, tuple(z_tst.shape)))
+    m = z_tst.shape[1]
+    _cond_hypers(lengthscale, outputscale, noise, P)
+    _cond_mean(mean_tst, mean_mode, B, P, m)
+    _cond_limits(n, cap, dt)
+    mu = torch.empty(B, m, dtype=dt, device=dev)
+    var = torch.empty(B, m, dtype=dt, device=dev) if want_var else None
+    with _Timed('gp_cond_predict'):
+        _check(lib.pacoh_gp_cond_predict(_ptr(zs), _ptr(X, zs), _ptr(alpha, zs), _ptr(info), _ptr(z_tst, zs), zt_div, _ptr(mean_tst, zs),
+                                         mean_mode, _ptr(lengthscale, zs), _ptr(outputscale, zs), _ptr(noise, zs), _ptr(mu), _ptr(var),
+                                         B, P, n, cap, m, _kf(f, kernel), dtype_code(zs), _stream()), 'pacoh_gp_cond_predict')
+    return mu, var
+
+
+def gp_cond_append(state, n, z_new, zn_div, mean_new, mean_mode, y_new, yn_div, lengthscale, outputscale, noise, B, P,
+                   kernel=KERNEL_RBF):
+    """append the k points z_new [B / zn_div, k, f], y_new [B / yn_div, k] to every conditioned problem in place (an O(n^2) bordered
+    update per point) -> fail int32 [B] on the device: 1 where the update was refused (s^2 <= 0); such a problem's rows < n are as
+    before and it has to be conditioned again on all points.  The caller's n becomes n + k."""
+    lib = load_library()
+    cap, f = _cond_state(state, B, P)
+    zs, resid, X, alpha, info = state
+    dev, dt = zs.device, zs.dtype
+    if z_new.dim() != 3 or z_new.shape[2] != f or z_new.shape[0] * zn_div < B or z_new.shape[1] < 1:
+        raise ValueError('z_new must be [>= %d,k,%d] for zn_div %d, got %s' % (-(-B // max(1, zn_div)), f, zn_div, tuple(z_new.shape)))
+    k = z_new.shape[1]
+    if y_new.dim() != 2 or y_new.shape[1] != k or y_new.shape[0] * yn_div < B:
+        raise ValueError('y_new must be [>= %d,%d] for yn_div %d, got %s' % (-(-B // max(1, yn_div)), k, yn_div, tuple(y_new.shape)))
+    _cond_hypers(lengthscale, outputscale, noise, P)
+    _cond_mean(mean_new, mean_mode, B, P, k)
+    _cond_limits(n, cap, dt, k)
+    fail = torch.zeros(B, dtype=torch.int32, device=dev)
+    with _Timed('gp_cond_append'):
+        _check(lib.pacoh_gp_cond_append(_ptr(zs), _ptr(resid, zs), _ptr(X, zs), _ptr(alpha, zs), _ptr(info), _ptr(z_new, zs), zn_div,
+                                        _ptr(mean_new, zs), mean_mode, _ptr(y_new, zs), yn_div, _ptr(lengthscale, zs),
+                                        _ptr(outputscale, zs), _ptr(noise, zs), _ptr(fail), B, P, n, cap, k, _kf(f, kernel),
+                                        dtype_code(zs), _stream()), 'pacoh_gp_cond_append')
+    return fail
 
 
 _DENSE_WS = {}

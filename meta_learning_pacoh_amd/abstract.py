@@ -177,6 +177,23 @@ class RegressionModelMetaLearned:
             metrics[ids] = torch.stack([ll.mean(1), rmse, calib], dim=1).double().cpu().numpy()
         return np.mean(metrics[:, 0]), np.mean(metrics[:, 1]), np.mean(metrics[:, 2])
 
+    # -- a posterior conditioned once: predict many times, append points (conditioned.py, csrc/gp_cond.hip) -----------------------
+    def condition(self, context_x, context_y, capacity=None, **kwargs):
+        """condition the model on a task's context ONCE -> ConditionedGP, whose .predict(test_x) / .confidence_intervals(test_x)
+        give what predict(context_x, context_y, test_x, **kwargs) gives without refactoring the kernel matrix, and whose
+        .append(x, y) adds points in O(n^2).  kwargs are those of predict(); the parameter rows are taken once, here (PACOH-VI in
+        'Bayes' mode draws its n_posterior_samples rows now, consuming the sampling stream as one predict() call would), and kept:
+        the object is a snapshot that later meta_fit() calls do not change.  capacity: the most points the object can grow to
+        (None: the size limit L.gp_cond_max_n(dtype)); a context or capacity beyond the limit raises RuntimeError.
+        Out of scope: joint covariance / log_prob / sample on the object, several tasks in one object, ragged contexts, the
+        single-task learner, contexts beyond the limit, gradients."""
+        from .conditioned import ConditionedGP
+        cx, cy = self._prepare_data_per_task(context_x, context_y)
+        theta, mixture, _ = self._loo_params(1, **kwargs)
+        state = self.engine.condition(theta, self._to_device(cx), self._to_device(cy), capacity)
+        _raise_not_psd(state.info)
+        return ConditionedGP(self.engine, state, mixture, self.x_mean, self.x_std, self.y_mean, self.y_std, self.dtype, self.device)
+
     def confidence_intervals(self, context_x, context_y, test_x, confidence=0.9, **kwargs):
         """abstract.py:183-204 -> (ucb, lcb)"""
         pred_dist = self.predict(context_x, context_y, test_x, return_density=True, **kwargs)

@@ -889,3 +889,73 @@ class GPEngine:
         z, z_div, mean, mode = self._features(theta, ctx_x.contiguous(), T, n, theta_per_task)
         return L.gp_loo(z, z_div, mean, mode, ctx_y.contiguous(), P, ls, os_, noise, T * P, rows, n_valid=n_valid,
                         kernel=self.layout.kernel_code)
+
+    # -- conditioned posterior: condition once, predict many times, append points (csrc/gp_cond.hip) --------------------------------
+    def condition(self, theta, ctx_x, ctx_y, capacity=None):
+        """condition ONE task's GP on ctx_x[n,d], ctx_y[n] for every parameter row of theta (B = P problems) and keep the factor:
+        -> CondState with a clone of the rows, their transformed hyper-parameters (computed once), the state buffers of
+        L.gp_condition with room for `capacity` points (None: L.gp_cond_max_n) and the normalised context on the device (for a
+        refit).  state.info[p] < 0: that row's kernel matrix was not positive definite on any jitter rung."""
+        theta = theta.detach().clone().contiguous()
+        n, d = ctx_x.shape
+        dt, dev = theta.dtype, theta.device
+        cap = L.gp_cond_max_n(dt) if capacity is None else int(capacity)
+        L._cond_limits(n, cap, dt)
+        st = CondState()
+        st.theta, st.hypers, st.n, st.cap = theta, self._hypers(theta), 0, cap
+        st.ctx_x = torch.zeros(cap, d, dtype=dt, device=dev)
+        st.ctx_y = torch.zeros(cap, dtype=dt, device=dev)
+        st.ctx_x[:n], st.ctx_y[:n] = ctx_x, ctx_y.reshape(-1)
+        st.bufs = self._cond_fit(st, n, None)
+        st.n = n
+        return st
+
+    def _cond_fit(self, st, n, bufs):
+        """L.gp_condition of the first n stored context points into bufs (None: fresh zero-filled buffers of the state's capacity)"""
+        P = st.theta.shape[0]
+        ls, os_, noise = st.hypers
+        z, z_div, mean, mode = self._features(st.theta, st.ctx_x[:n].unsqueeze(0).contiguous(), 1, n)
+        return L.gp_condition(z, z_div, mean, mode, st.ctx_y[:n].reshape(1, n).contiguous(), P, ls, os_, noise, P, P,
+                              capacity=st.cap, state=bufs, kernel=self.layout.kernel_code)
+
+    def cond_predict(self, st, tst_x, want_var=True):
+        """posterior predictive of the conditioned task at tst_x[m,d] for every parameter row: mu[P,m], var[P,m] (normalised space,
+        observation noise included) -- no factorisation, one launch over P x ceil(m / 64) workgroups"""
+        P = st.theta.shape[0]
+        m = tst_x.shape[0]
+        ls, os_, noise = st.hypers
+        zt, zt_div, mt, mode = self._features(st.theta, tst_x.unsqueeze(0).contiguous(), 1, m)
+        return L.gp_cond_predict(st.bufs, st.n, zt, zt_div, mt, mode, ls, os_, noise, P, P, want_var=want_var,
+                                 kernel=self.layout.kernel_code)
+
+    def cond_append(self, st, x_new, y_new):
+        """append x_new[k,d], y_new[k] to the conditioned task in place (O(n^2) per point and row) -> fail int32 [P] on the device;
+        rows whose update was refused need cond_refit.  Raises before anything changes when the capacity is exceeded."""
+        P = st.theta.shape[0]
+        k = x_new.shape[0]
+        if k < 1 or st.n + k > st.cap:
+            raise RuntimeError('appending %d point(s) to %d exceeds the capacity of %d of this conditioned GP (limit of %d points for %s)'
+                               % (k, st.n, st.cap, L.gp_cond_max_n(st.theta.dtype), st.theta.dtype))
+        ls, os_, noise = st.hypers
+        z, z_div, mean, mode = self._features(st.theta, x_new.unsqueeze(0).contiguous(), 1, k)
+        fail = L.gp_cond_append(st.bufs, st.n, z, z_div, mean, mode, y_new.reshape(1, k).contiguous(), P, ls, os_, noise, P, P,
+                                kernel=self.layout.kernel_code)
+        st.ctx_x[st.n:st.n + k], st.ctx_y[st.n:st.n + k] = x_new, y_new.reshape(-1)
+        st.n += k
+        return fail
+
+    def cond_refit(self, st):
+        """condition again on all st.n stored points, from scratch (the jitter ladder applies), into FRESH buffers that replace the
+        state's only when the launch has been issued: the state is never half-updated"""
+        st.bufs = self._cond_fit(st, st.n, None)
+        return st
+
+
+class CondState:
+    """what GPEngine.condition keeps of one task: theta [P,D] (a clone), hypers (lengthscale, outputscale, noise), bufs = (zs, resid,
+    X, alpha, info) of L.gp_condition, n points in use of cap, and the normalised context ctx_x[cap,d], ctx_y[cap] for a refit"""
+    __slots__ = ('theta', 'hypers', 'bufs', 'n', 'cap', 'ctx_x', 'ctx_y')
+
+    @property
+    def info(self):
+        return self.bufs[4]
