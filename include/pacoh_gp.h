@@ -513,7 +513,7 @@ int pacoh_svgd_update_next(void* X, const void* score, const void* prior_mean, c
                            int bandwidth_ready, int dtype, void* stream);
 
 /* Distinct tasks of a step's draw.  A step's tb tasks are drawn WITH replacement (GPR_meta_svgd.py:102): a draw of 1024 from 1024
- * tasks holds ~647 distinct ones, and every repeated draw recomputes the same numbers.  The host rewrites each row of idx_all as the
+ * tasks holds ~647 distinct ones, and every repeated draw recomputes the same numbers.  The feed rewrites each row of idx_all (pacoh_distinct_rows, below) as the
  * row's distinct task ids in order of first occurrence (padded to tb with any valid id), with nact_all[row] = how many they are and
  * mult_all[row, tb] = how often each was drawn (`dtype` values, 0 for the padding):  sum_{draws t} g(t, p) = sum_{distinct u}
  * mult[u] g(u, p).  The launch that gathers a row's tasks also copies its nact / mult entries into the fixed buffers n_act[1] /
@@ -572,6 +572,18 @@ int pacoh_svgd_update_next_active(const pacoh_active_feed* feed, void* X, const 
                                   int32_t* out_n_valid, int n, int d,
                                   int off_ls, int f, int off_os, int off_noise, double noise_floor, void* ls, void* os, void* noise,
                                   int bandwidth_ready, int dtype, void* stream);
+/* The rewrite itself, on the device (csrc/distinct.hip): every one of the k rows idx[k, tb] of task ids in [0, n_tasks) -> rows[k, tb]
+ * (the row's distinct ids in order of first occurrence, padded with the row's first id), mult[k, tb] (`dtype` values: how often each
+ * was drawn, 0 for the padding) and n_act[k].  One workgroup per row, integer arithmetic only: the output is deterministic and equal,
+ * element for element, to the host's stable-sort version (engine.distinct_rows).  rows == idx rewrites the draws in place; otherwise
+ * the two must not overlap.  An id outside [0, n_tasks) is read as the nearest valid one.
+ * Returns PACOH_DECLINED -- nothing launched, no buffer touched, not an error -- when tb > PACOH_DISTINCT_MAX_DRAWS or n_tasks >
+ * PACOH_DISTINCT_MAX_TASKS (the row's tables live in LDS): the caller then rewrites the rows on the host. */
+#define PACOH_DECLINED 1
+#define PACOH_DISTINCT_MAX_DRAWS 4096
+#define PACOH_DISTINCT_MAX_TASKS 8192
+int pacoh_distinct_rows(const int64_t* idx, int64_t* rows, void* mult, int32_t* n_act, int k, int tb, int n_tasks, int dtype,
+                        void* stream);
 /* The device-side re-split of the fused networks' tile range (csrc/mlp_fused_split.h), for tests: tiles per workgroup when tiles_eff
  * of the tiles_full tiles the launch was planned for (wgs workgroups of tpw_host tiles each) are live. */
 int pacoh_mlp_fused_split(int tiles_eff, int tiles_full, int wgs, int tpw_host);

@@ -145,7 +145,7 @@ class _RandomGPLearner(StepDriver, RegressionModelMetaLearned):
                    for d_out in (1, lay.feature_dim)):
             return
         if force == '1' or tb_local * rows >= self.DEDUP_MIN_PROBLEMS:
-            self._feed.enable_dedup()
+            self._feed.enable_dedup(self.tasks.T)
 
     def _idx_uploader(self):
         up = getattr(self, '_idx_up', None)

@@ -79,6 +79,7 @@ SIGNATURES = {
     'pacoh_hyper_bwd': (_i, [_vp, _l, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _d, _vp, _vp, _vp, _i, _i, _vp, _i, _vp]),
     'pacoh_step_select': (_i, [_vp, _i, _vp, _i, _vp, _l, _vp, _vp, _vp, _vp, _i, _vp]),
     'pacoh_scale_dev': (_i, [_vp, _vp, _l, _i, _vp]),
+    'pacoh_distinct_rows': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'pacoh_step_begin': (_i, [_vp, _i, _vp, _i, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i,
                               _vp, _l, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     'pacoh_step_begin_vi': (_i, [_vp, _i, _vp, _i, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i,
@@ -1270,6 +1271,27 @@ def scale_dev(buf, scalar):
     """buf *= scalar[0] with the scalar in device memory"""
     with _Timed('scale_dev'):
         _check(load_library().pacoh_scale_dev(_ptr(buf), _ptr(scalar, buf), buf.numel(), dtype_code(buf), _stream()), 'pacoh_scale_dev')
+
+
+DECLINED = 1                                                    # PACOH_DECLINED
+DISTINCT_MAX_DRAWS, DISTINCT_MAX_TASKS = 4096, 8192             # PACOH_DISTINCT_MAX_*
+
+
+def distinct_rows(idx, mult, n_act, n_tasks, rows=None):
+    """every row of the task draws idx [k, tb] (int64, ids in [0, n_tasks)) as its distinct tasks, on the device: rows [k, tb] (None:
+    idx is rewritten in place), mult [k, tb] (float32 / float64) and n_act [k] (int32) as engine.distinct_rows gives them, element for
+    element; one launch on the current stream -> True, or False when the library declines the shape (tb > DISTINCT_MAX_DRAWS or
+    n_tasks > DISTINCT_MAX_TASKS): then nothing was launched and no buffer touched"""
+    rows = idx if rows is None else rows
+    k, tb = idx.shape
+    assert idx.dtype == rows.dtype == torch.int64 and n_act.dtype == torch.int32
+    assert rows.shape == idx.shape == mult.shape and n_act.numel() == k
+    rc = load_library().pacoh_distinct_rows(_ptr(idx), _ptr(rows), _ptr(mult), _ptr(n_act), k, tb, int(n_tasks), dtype_code(mult),
+                                            _stream())
+    if rc == DECLINED:
+        return False
+    _check(rc, 'pacoh_distinct_rows')
+    return True
 
 
 def svgd_update_dev(X, score, prior_mean, prior_std, prior_factor, bandwidth, optimizer, scalars, exp_avg, exp_avg_sq,

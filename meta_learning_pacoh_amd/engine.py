@@ -187,11 +187,13 @@ class StepFeed:
     the first launch of the captured step -- moves the current row into the fixed buffers idx / sc / aux the kernels read and
     advances the device-side counter.
     dedup (set by the learner before the first upload; PACOH-SVGD on the throughput kernels): upload() rewrites every row of task
-    draws as its distinct tasks (distinct_rows) with mult_all[chunk, tb] / nact_all[chunk] beside idx_all; whoever gathers a row's
-    tasks publishes its entries in the fixed buffers mult [tb] / nact [1] the step's kernels read (active())."""
+    draws as its distinct tasks with mult_all[chunk, tb] / nact_all[chunk] beside idx_all -- on the device, by one launch behind the
+    copy of the raw draws (L.distinct_rows); on the host (distinct_rows, the specification) where that launch declines the shape or
+    PACOH_DEDUP_HOST=1 asks for it; whoever gathers a row's tasks publishes its entries in the fixed buffers mult [tb] / nact [1]
+    the step's kernels read (active())."""
 
     _warned_threads = False
-    dedup = False
+    dedup = dedup_on_device = False
 
     def __init__(self, device, dtype, tb, chunk=1024, aux_shape=None):
         if not StepFeed._warned_threads:
@@ -230,8 +232,9 @@ class StepFeed:
         self._n_aux = [t.numpy() for t in self._h_aux] if self._h_aux is not None else None
         self.mult_all = self.nact_all = self.mult = self.nact = None
 
-    def enable_dedup(self):
-        """evaluate every distinct task of a step's draw once (before the first upload)"""
+    def enable_dedup(self, n_tasks=None):
+        """evaluate every distinct task of a step's draw once (before the first upload).  n_tasks: the draws are task numbers below
+        it -- what the device-side rewrite sizes its tables by (None: the rows are rewritten on the host)"""
         assert self.tb > 0 and self._ev[0] is None and self._ev[1] is None
         rows = self.idx_all.shape[0]
         self.dedup = True
@@ -239,10 +242,23 @@ class StepFeed:
         self.nact_all = torch.full((rows,), self.tb, dtype=torch.int32, device=self.device)
         self.mult = torch.ones(self.tb, dtype=self.dtype, device=self.device)
         self.nact = torch.full((1,), self.tb, dtype=torch.int32, device=self.device)
-        self._h_mult = [torch.zeros(rows, self.tb, dtype=self.dtype).pin_memory() for _ in range(2)]
-        self._h_nact = [torch.zeros(rows, dtype=torch.int32).pin_memory() for _ in range(2)]
-        self._n_mult = [t.numpy() for t in self._h_mult]
-        self._n_nact = [t.numpy() for t in self._h_nact]
+        self._n_tasks = n_tasks
+        self.dedup_on_device = n_tasks is not None and os.environ.get('PACOH_DEDUP_HOST', '0') != '1'
+        self._h_mult = self._h_nact = None                # pinned staging of the host-side rewrite: _dedup_on_host
+
+    def _dedup_on_host(self, q, idx_rows, k, kk):
+        """the rewrite by distinct_rows on the host: the chunk's k rows into staging set q (rows k .. kk repeat the last one) and the
+        copies of their counts; the caller copies the ids"""
+        if self._h_mult is None:
+            rows = self.idx_all.shape[0]
+            self._h_mult = [torch.zeros(rows, self.tb, dtype=self.dtype).pin_memory() for _ in range(2)]
+            self._h_nact = [torch.zeros(rows, dtype=torch.int32).pin_memory() for _ in range(2)]
+        nm, nn = self._h_mult[q].numpy(), self._h_nact[q].numpy()
+        self._n_idx[q][:k], hm, hn = distinct_rows(idx_rows, nm.dtype)
+        nm[:k], nn[:k] = hm, hn
+        nm[k:kk], nn[k:kk] = hm[k - 1], hn[k - 1]
+        self.mult_all[:kk].copy_(self._h_mult[q][:kk], non_blocking=True)
+        self.nact_all[:kk].copy_(self._h_nact[q][:kk], non_blocking=True)
 
     def active(self):
         """(nact, mult) for the kernels of a step (GPEngine.lml_and_grad(active=...)), or None"""
@@ -269,16 +285,24 @@ class StepFeed:
         self.sc_all[:kk].copy_(self._h_sc[q][:kk], non_blocking=True)
         if self.tb > 0:
             hi = self._n_idx[q]
-            if self.dedup:
-                hi[:k], hm, hn = distinct_rows(np.asarray(idx_rows).reshape(k, self.tb), self._n_mult[q].dtype)
-                self._n_mult[q][:k], self._n_nact[q][:k] = hm, hn
-                self._n_mult[q][k:kk], self._n_nact[q][k:kk] = hm[k - 1], hn[k - 1]
-                self.mult_all[:kk].copy_(self._h_mult[q][:kk], non_blocking=True)
-                self.nact_all[:kk].copy_(self._h_nact[q][:kk], non_blocking=True)
+            idx_rows = np.asarray(idx_rows).reshape(k, self.tb)
+            if self.dedup and not self.dedup_on_device:
+                self._dedup_on_host(q, idx_rows, k, kk)
             else:
-                hi[:k] = np.asarray(idx_rows).reshape(k, self.tb)
+                hi[:k] = idx_rows
             hi[k:kk] = hi[k - 1]
             self.idx_all[:kk].copy_(self._h_idx[q][:kk], non_blocking=True)
+            if self.dedup and self.dedup_on_device:
+                # the raw draws are on their way: ONE launch behind the copy rewrites them in place and fills the counts
+                if not L.distinct_rows(self.idx_all[:kk], self.mult_all[:kk], self.nact_all[:kk], self._n_tasks):
+                    # declined (more draws per step or more tasks than its tables hold: the same for every chunk of this feed), and
+                    # nothing was touched: from here on the host rewrites the rows.  This chunk's staging set is rewritten once the
+                    # copy above has read it
+                    self.dedup_on_device = False
+                    torch.cuda.current_stream().synchronize()
+                    self._dedup_on_host(q, idx_rows, k, kk)
+                    hi[k:kk] = hi[k - 1]
+                    self.idx_all[:kk].copy_(self._h_idx[q][:kk], non_blocking=True)
         if self.aux_all is not None:
             ha = self._n_aux[q]
             on_device = isinstance(aux_rows, str)
