@@ -212,6 +212,38 @@ int pacoh_gp_cond_append(void* zs, void* resid, void* X, void* alpha, const int3
                          const void* lengthscale, const void* outputscale, const void* noise, int32_t* fail,
                          int B, int P, int n, int cap, int k, int f, int dtype, void* stream);
 
+/* ---- pathwise posterior function draws on the conditioned state (csrc/gp_path.hip) ----------------------------------------------
+ * Matheron's rule on a random-Fourier-feature prior (Wilson et al. 2020).  With u = z / lengthscale, D features
+ *   phi_d(u) = sqrt(2 os / D) cos(omega_d . u + phase_d),     omega[D,f] (scaled coordinates), phase[D], shared by all problems,
+ * and S draws per problem, w[B,S,D] and eps[B,S,n] standard normal, a posterior function draw is
+ *   f_s(x*) = m(x*) + sum_d phi_d(u*) w_sd + sum_i os k(u*, u_i) v_si,
+ *   v_s     = (K + j I)^-1 (resid - Phi(zs) w_s - sqrt(noise + j) eps_s),
+ * K, j = the jitter of the rung in info[b], X = L^-1, resid and zs exactly as pacoh_gp_condition leaves the state and
+ * pacoh_gp_cond_append grows it (n points in use of cap).  No m x m object, no factorisation, any m.
+ * Families: RBF (omega ~ N(0, I)) and Matern nu = 1/2, 3/2, 5/2 (omega = g / sqrt(u / 2 nu), g ~ N(0, I), u ~ chi^2(2 nu)): the
+ * caller draws omega.  The cosine family has no such spectral form for f > 1: PACOH_ELIMIT.
+ * Conventions as pacoh_gp_cond_predict: family in the bits above `f`, outputscale NULL = 1, mean modes, zt_div sharing,
+ * info[b] < 0 writes NaN into that problem's v / out; every limit is checked before anything is enqueued.
+ * Limits (else PACOH_ELIMIT): 1 <= n <= cap <= pacoh_gp_cond_max_n(dtype), f <= 16, S >= 1, m >= 1, 16 <= D <= 16384 with
+ * D % 16 == 0, grids up to 2^31 - 1 workgroups.  NULL pointers (outputscale and, for PACOH_MEAN_ZERO, mean_tst aside), B, P,
+ * zt_div <= 0: PACOH_EINVAL; a bad dtype is PACOH_EDTYPE, looked at first.
+ *
+ * pacoh_gp_path_fit:  v[B,S,n] (rows of n, NOT of cap) = X^T (X R), R = resid - Phi(zs) w - sqrt(noise + j) eps.  One workgroup per
+ *   (problem, 16 draws); X is read at stride cap, at or below the diagonal and below row n only.  Once per set of draws.
+ * pacoh_gp_path_eval: out[B,S,m] = the S draws at the m test points z_tst[B/zt_div,m,f] in normalised space -- the LATENT f, no
+ *   observation noise.  One GEMM [m x (D + n)] . [(D + n) x S] on the matrix cores, its left operand (features, then kernel
+ *   columns) computed on the fly; grid = problems x tiles of 64 test points x groups of up to 64 draws.  The cosine is evaluated
+ *   with full-range argument reduction (Matern-1/2 frequencies are Cauchy-tailed). */
+int pacoh_gp_path_fit(const void* zs, const void* resid, const void* X, const int32_t* info,
+                      const void* outputscale, const void* noise,
+                      const void* omega, const void* phase, const void* w, const void* eps, void* v,
+                      int B, int P, int n, int cap, int S, int D, int f, int dtype, void* stream);
+int pacoh_gp_path_eval(const void* zs, const void* v, const void* w, const int32_t* info,
+                       const void* omega, const void* phase,
+                       const void* z_tst, int zt_div, const void* mean_tst, int mean_mode,
+                       const void* lengthscale, const void* outputscale, void* out,
+                       int B, int P, int n, int cap, int S, int D, int m, int f, int dtype, void* stream);
+
 /* ---- dense path (large n): Cholesky-based Gaussian log-density of materialised covariances -----
  * logp[b] = log N(resid[b]; 0, A[b]) * scale,  A[B,n,n] symmetric (lower triangle read), destroyed
  * (overwritten by its Cholesky factor).  With A from pacoh_gram_rbf_ard(..., add_noise_diag=1) and

@@ -10,3 +10,4 @@ from .GPR_meta_svgd import GPRegressionMetaLearnedSVGD     # noqa: E402,F401
 from .GPR_meta_vi import GPRegressionMetaLearnedVI         # noqa: E402,F401
 from .GPR_mll import GPRegressionLearned                   # noqa: E402,F401
 from .conditioned import ConditionedGP                     # noqa: E402,F401
+from .paths import PosteriorPaths                          # noqa: E402,F401

@@ -43,6 +43,9 @@ SIGNATURES = {
     'pacoh_gp_cond_predict': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'pacoh_gp_cond_append': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp,
                                   _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'pacoh_gp_path_fit': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'pacoh_gp_path_eval': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp,
+                                _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'pacoh_gp_lml_fwdbwd': (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                  _i, _i, _i, _i, _i, _vp]),
     'pacoh_gp_predict_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
@@ -559,6 +562,86 @@ def gp_cond_append(state, n, z_new, zn_div, mean_new, mean_mode, y_new, yn_div, 
                                         _ptr(outputscale, zs), _ptr(noise, zs), _ptr(fail), B, P, n, cap, k, _kf(f, kernel),
                                         dtype_code(zs), _stream()), 'pacoh_gp_cond_append')
     return fail
+
+
+PATH_MIN_FEATURES, PATH_MAX_FEATURES = 16, 16384      # random Fourier features per draw: a multiple of 16 in this range
+
+
+def _path_base(omega, phase, w, eps, B, n, f, dt):
+    """shapes of a draw base (omega [D,f], phase [D], w [B,S,D], eps [B,S,n]) -> S, D"""
+    if omega.dim() != 2 or omega.shape[1] != f:
+        raise ValueError('omega must be [D,%d], got %s' % (f, tuple(omega.shape)))
+    D = omega.shape[0]
+    if D < PATH_MIN_FEATURES or D > PATH_MAX_FEATURES or D % 16:
+        raise ValueError('the number of random features must be a multiple of 16 in [%d, %d], got %d'
+                         % (PATH_MIN_FEATURES, PATH_MAX_FEATURES, D))
+    if tuple(phase.shape) != (D,):
+        raise ValueError('phase must be [%d], got %s' % (D, tuple(phase.shape)))
+    if w.dim() != 3 or w.shape[0] != B or w.shape[2] != D or w.shape[1] < 1:
+        raise ValueError('w must be [%d,S,%d], got %s' % (B, D, tuple(w.shape)))
+    S = w.shape[1]
+    if eps is not None and tuple(eps.shape) != (B, S, n):
+        raise ValueError('eps must be [%d,%d,%d], got %s' % (B, S, n, tuple(eps.shape)))
+    for name, t in (('omega', omega), ('phase', phase), ('w', w), ('eps', eps)):
+        if t is not None and t.dtype != dt:
+            raise TypeError('mixed dtypes in one PACOH call: %s is %s, the state %s' % (name, t.dtype, dt))
+    return S, D
+
+
+def _path_family(kernel):
+    if kernel == KERNEL_COSINE:
+        raise NotImplementedError('pathwise draws need a spectral density: the cosine kernel family has none of this form')
+
+
+def gp_path_fit(state, n, omega, phase, w, eps, outputscale, noise, B, P, kernel=KERNEL_RBF):
+    """the pathwise update of S posterior function draws per conditioned problem (Matheron's rule on D random Fourier features):
+    v [B,S,n] = (K + j I)^-1 (resid - Phi(zs) w - sqrt(noise + j) eps) through the state's X, for the base omega [D,f], phase [D],
+    w [B,S,D], eps [B,S,n] (info < 0: NaN).  One launch, no factorisation."""
+    lib = load_library()
+    _path_family(kernel)
+    cap, f = _cond_state(state, B, P)
+    zs, resid, X, alpha, info = state
+    S, D = _path_base(omega, phase, w, eps, B, n, f, zs.dtype)
+    if noise.numel() != P or (outputscale is not None and outputscale.numel() != P):
+        raise ValueError('noise and outputscale must be [%d]' % P)
+    _cond_limits(n, cap, zs.dtype)
+    v = torch.empty(B, S, n, dtype=zs.dtype, device=zs.device)
+    with _Timed('gp_path_fit'):
+        _check(lib.pacoh_gp_path_fit(_ptr(zs), _ptr(resid, zs), _ptr(X, zs), _ptr(info), _ptr(outputscale, zs), _ptr(noise, zs),
+                                     _ptr(omega, zs), _ptr(phase, zs), _ptr(w, zs), _ptr(eps, zs), _ptr(v), B, P, n, cap, S, D,
+                                     _kf(f, kernel), dtype_code(zs), _stream()), 'pacoh_gp_path_fit')
+    return v
+
+
+def gp_path_eval(zs, n, v, omega, phase, w, info, z_tst, zt_div, mean_tst, mean_mode, lengthscale, outputscale, B, P,
+                 kernel=KERNEL_RBF):
+    """the S draws of gp_path_fit at z_tst [B / zt_div, m, f] -> out [B,S,m] in normalised space, the LATENT function (no observation
+    noise); zs [B,cap,f] the state's scaled context (its first n rows are read), v [B,S,n].  One GEMM on the matrix cores whose left
+    operand (features, kernel columns) is computed on the fly; info < 0: NaN."""
+    lib = load_library()
+    _path_family(kernel)
+    if zs.dim() != 3 or zs.shape[0] != B or B <= 0 or P <= 0 or B % P:
+        raise ValueError('zs must be [B,cap,f] with B = %d a positive multiple of P = %d, got %s' % (B, P, tuple(zs.shape)))
+    cap, f = zs.shape[1], zs.shape[2]
+    dt, dev = zs.dtype, zs.device
+    S, D = _path_base(omega, phase, w, None, B, n, f, dt)
+    if tuple(v.shape) != (B, S, n) or v.dtype != dt:
+        raise ValueError('v must be %s [%d,%d,%d], got %s %s' % (dt, B, S, n, v.dtype, tuple(v.shape)))
+    if info.dtype != torch.int32 or info.numel() != B:
+        raise ValueError('info must be int32 [%d]' % B)
+    if z_tst.dim() != 3 or z_tst.shape[2] != f or z_tst.shape[0] * zt_div < B or z_tst.shape[1] < 1:
+        raise ValueError('z_tst must be [>= %d,m,%d] for zt_div %d, got %s' % (-(-B // max(1, zt_div)), f, zt_div, tuple(z_tst.shape)))
+    m = z_tst.shape[1]
+    if tuple(lengthscale.shape) != (P, f) or (outputscale is not None and outputscale.numel() != P):
+        raise ValueError('lengthscale must be [%d,%d], outputscale [%d]' % (P, f, P))
+    _cond_mean(mean_tst, mean_mode, B, P, m)
+    _cond_limits(n, cap, dt)
+    out = torch.empty(B, S, m, dtype=dt, device=dev)
+    with _Timed('gp_path_eval'):
+        _check(lib.pacoh_gp_path_eval(_ptr(zs), _ptr(v, zs), _ptr(w, zs), _ptr(info), _ptr(omega, zs), _ptr(phase, zs), _ptr(z_tst, zs),
+                                      zt_div, _ptr(mean_tst, zs), mean_mode, _ptr(lengthscale, zs), _ptr(outputscale, zs), _ptr(out),
+                                      B, P, n, cap, S, D, m, _kf(f, kernel), dtype_code(zs), _stream()), 'pacoh_gp_path_eval')
+    return out
 
 
 _DENSE_WS = {}

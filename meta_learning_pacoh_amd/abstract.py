@@ -185,8 +185,9 @@ class RegressionModelMetaLearned:
         'Bayes' mode draws its n_posterior_samples rows now, consuming the sampling stream as one predict() call would), and kept:
         the object is a snapshot that later meta_fit() calls do not change.  capacity: the most points the object can grow to
         (None: the size limit L.gp_cond_max_n(dtype)); a context or capacity beyond the limit raises RuntimeError.
-        Out of scope: joint covariance / log_prob / sample on the object, several tasks in one object, ragged contexts, the
-        single-task learner, contexts beyond the limit, gradients."""
+        .sample_paths(num_paths) draws posterior functions (pathwise conditioning, paths.py) that evaluate at any number of points.
+        Out of scope: joint covariance / log_prob on the object, pathwise draws for the cosine family, several tasks in one object,
+        ragged contexts, the single-task learner, contexts beyond the limit, gradients."""
         from .conditioned import ConditionedGP
         cx, cy = self._prepare_data_per_task(context_x, context_y)
         theta, mixture, _ = self._loo_params(1, **kwargs)

@@ -3,17 +3,21 @@
     cond = model.condition(context_x, context_y)          # Gram, jittered Cholesky and L^-1: once
     mean, std = cond.predict(candidates)                   # no factorisation: a Gram tile and a triangular GEMM on the matrix cores
     cond.append(x_new, y_new)                              # bordered update of the stored factor
+    paths = cond.sample_paths(16)                          # posterior function draws (paths.py): paths(candidates) -> [P * 16, m]
 
 What predict() of the learners recomputes on every call (csrc/gp_cond.hip keeps it: the rows of L^-1 and alpha) is what gpytorch
 caches in its prediction strategy and updates in ExactGP.get_fantasy_model; the reference itself never reuses them.
 
-Out of scope: the joint covariance (so no log_prob and no sample on this object: use predict(..., return_density=True) of the
-learner), several tasks in one object, ragged contexts (n_valid), the single-task learner GPRegressionLearned, contexts beyond
-_lib.gp_cond_max_n(dtype) points (there is no large-context path), and gradients."""
+Out of scope: the joint covariance (so no log_prob on this object: use predict(..., return_density=True) of the learner; joint
+DRAWS come from sample_paths(), which needs no covariance), the cosine kernel family in sample_paths(), several tasks in one object,
+ragged contexts (n_valid), the single-task learner GPRegressionLearned, contexts beyond _lib.gp_cond_max_n(dtype) points (there is
+no large-context path), and gradients."""
 import numpy as np
 import torch
 
+from . import _lib as L
 from .distributions import GaussianPredictive
+from .paths import PosteriorPaths, check_base, draw_base
 from .util import _handle_input_dimensionality
 
 
@@ -79,3 +83,30 @@ class ConditionedGP:
             self._engine.cond_refit(self._state)
             _raise_not_psd(self._state.info)
         return self
+
+    def sample_paths(self, num_paths, num_features=1024, base=None, like=None):
+        """num_paths posterior FUNCTION draws per parameter row by pathwise conditioning on num_features random Fourier features
+        (paths.py) -> PosteriorPaths: paths(test_x) evaluates all of them at any number of points in one launch, without a joint
+        covariance.  The fit costs two triangular products with the stored factor, once.
+        base = (omega [D,f], phase [D], w [P,S,D], eps [P,S,n]) on the device: used as it is (shapes are checked, no random number is
+        drawn).  like = an earlier PosteriorPaths of this object with the same num_paths and num_features: its omega, phase, w and
+        eps columns are kept and eps is drawn only for the points appended since, so a loop follows the same prior functions as data
+        arrive.  Otherwise the base comes from torch's device generator in the fixed order of paths.draw_base.
+        The cosine kernel family raises NotImplementedError."""
+        lay = self._engine.layout
+        st = self._state
+        P, S, D, f = st.theta.shape[0], int(num_paths), int(num_features), lay.feature_dim
+        L._path_family(lay.kernel_code)
+        if S < 1:
+            raise ValueError('num_paths must be at least 1, got %d' % S)
+        if D < L.PATH_MIN_FEATURES or D > L.PATH_MAX_FEATURES or D % 16:
+            raise ValueError('num_features must be a multiple of 16 in [%d, %d], got %d' % (L.PATH_MIN_FEATURES, L.PATH_MAX_FEATURES, D))
+        if base is not None and like is not None:
+            raise ValueError('give base= or like=, not both')
+        if base is not None:
+            base = check_base(base, D, f, P, S, st.n, self._dtype, self._device)
+        else:
+            base = draw_base(lay.kernel_code, D, f, P, S, st.n, self._dtype, self._device,
+                             like=None if like is None else like.base)
+        snap = self._engine.cond_paths(st, base)
+        return PosteriorPaths(self._engine, snap, self._norm_x, self._y_mean.reshape(-1)[0], self._y_std.reshape(-1)[0])

@@ -974,6 +974,38 @@ class GPEngine:
         st.bufs = self._cond_fit(st, st.n, None)
         return st
 
+    # -- pathwise posterior function draws on the conditioned state (csrc/gp_path.hip) -----------------------------------------------
+    def cond_paths(self, st, base):
+        """fit S posterior function draws per parameter row to the conditioned task: base = (omega [D,f], phase [D], w [P,S,D],
+        eps [P,S,n]) on the device (paths.draw_base) -> PathSnap, a snapshot that shares nothing with st: its own copy of the rows,
+        the hyper-parameters, zs[:, :n], info, the base, and v [P,S,n] of L.gp_path_fit (one launch, no factorisation)"""
+        P, n = st.theta.shape[0], st.n
+        omega, phase, w, eps = base
+        ls, os_, noise = st.hypers
+        snap = PathSnap()
+        snap.v = L.gp_path_fit(st.bufs, n, omega, phase, w, eps, os_, noise, P, P, kernel=self.layout.kernel_code)
+        snap.theta, snap.n = st.theta.clone(), n
+        snap.hypers = tuple(None if h is None else h.clone() for h in st.hypers)
+        snap.zs, snap.info = st.bufs[0][:, :n].contiguous(), st.bufs[4].clone()
+        snap.omega, snap.phase, snap.w, snap.eps = (t.clone() for t in base)
+        return snap
+
+    def cond_paths_eval(self, snap, tst_x):
+        """the draws of a PathSnap at tst_x[m,d] -> [P,S,m] in normalised space (the latent function: no observation noise); the test
+        features and means as cond_predict takes them, one launch over P x ceil(m / 64) x ceil(S / 64) workgroups"""
+        P = snap.theta.shape[0]
+        m = tst_x.shape[0]
+        ls, os_, _ = snap.hypers
+        zt, zt_div, mt, mode = self._features(snap.theta, tst_x.unsqueeze(0).contiguous(), 1, m)
+        return L.gp_path_eval(snap.zs, snap.n, snap.v, snap.omega, snap.phase, snap.w, snap.info, zt, zt_div, mt, mode, ls, os_, P, P,
+                              kernel=self.layout.kernel_code)
+
+
+class PathSnap:
+    """what GPEngine.cond_paths keeps of one set of draws: theta [P,D], hypers, zs [P,n,f], info [P], n, the base (omega, phase, w,
+    eps) and the fitted v [P,S,n]"""
+    __slots__ = ('theta', 'hypers', 'zs', 'info', 'n', 'omega', 'phase', 'w', 'eps', 'v')
+
 
 class CondState:
     """what GPEngine.condition keeps of one task: theta [P,D] (a clone), hypers (lengthscale, outputscale, noise), bufs = (zs, resid,
