@@ -604,6 +604,24 @@ int pacoh_svgd_update_next_active(const pacoh_active_feed* feed, void* X, const 
                                   int32_t* out_n_valid, int n, int d,
                                   int off_ls, int f, int off_os, int off_noise, double noise_floor, void* ls, void* os, void* noise,
                                   int bandwidth_ready, int dtype, void* stream);
+/* The two networks' forward INSIDE the task-GP launch (csrc/gp_fwd_reg.hip): pacoh_mlp2_fwd_svgd[_active] followed by
+ * pacoh_gp_lml_fwdbwd[_active] with z = the kernel network's output (z_div = 1) and the mean network's output as a mean vector, as
+ * ONE launch in which every (task, particle) problem runs the networks on its own 64 rows -- z and the mean are not written to
+ * memory, every other output (lml, d_z [B,64,f], d_mean [B,64], d_lengthscale, d_noise, info, the activation stash the matching
+ * pacoh_mlp2_bwd_hyper reads) is the same bits as the two calls'.  The mean network's block starts at element off_mean of a theta
+ * row (d_out 1), the kernel network's at off_kernel (d_out f); act == NULL: every task is evaluated; svgd_X == NULL: no particle
+ * distances / counter increment (pacoh_mlp2_fwd instead of pacoh_mlp2_fwd_svgd); stash == NULL: none kept.
+ * pacoh_fwd_gp_applicable (host only, 1 / 0): fp32, RBF without outputscale, f <= 2, n == 64, x_div == P, d_in <= 4, one or two
+ * hidden layers of width <= 32 on the fused MLP path, mean_mode == PACOH_MEAN_VECTOR.  The call returns PACOH_ELIMIT elsewhere. */
+int pacoh_fwd_gp_applicable(int B, int P, int n, int x_div, int d_in, const int32_t* hidden, int n_hidden, int f,
+                            int has_outputscale, int mean_mode, int dtype);
+int pacoh_fwd_gp_lml_fwdbwd(const pacoh_active_tasks* act, const void* x, int x_div, const void* theta, long theta_stride, int P,
+                            int d_in, const int32_t* hidden, int n_hidden, long off_mean, long off_kernel, void* stash,
+                            const void* svgd_X, void* svgd_workspace, int svgd_P, int svgd_D, int64_t* counter,
+                            const void* y, int y_div, const void* lengthscale, const void* outputscale, const void* noise,
+                            const int32_t* n_valid, const void* g_lml, void* lml, void* d_z, void* d_mean,
+                            void* d_lengthscale, void* d_outputscale, void* d_noise, int32_t* info,
+                            int B, int n, int f, int dtype, void* stream);
 /* The rewrite itself, on the device (csrc/distinct.hip): every one of the k rows idx[k, tb] of task ids in [0, n_tasks) -> rows[k, tb]
  * (the row's distinct ids in order of first occurrence, padded with the row's first id), mult[k, tb] (`dtype` values: how often each
  * was drawn, 0 for the padding) and n_act[k].  One workgroup per row, integer arithmetic only: the output is deterministic and equal,

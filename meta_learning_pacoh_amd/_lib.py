@@ -132,6 +132,9 @@ SIGNATURES = {
     'pacoh_comm_init': (_i, [_vp, _i, _i, _c.POINTER(_vp)]),
     'pacoh_allreduce_sum': (_i, [_vp, _l, _i, _vp, _vp]),
     'pacoh_comm_destroy': (_i, [_vp]),
+    'pacoh_fwd_gp_applicable': (_i, [_i, _i, _i, _i, _i, _ip, _i, _i, _i, _i, _i]),
+    'pacoh_fwd_gp_lml_fwdbwd': (_i, [_vp, _vp, _i, _vp, _l, _i, _i, _ip, _i, _l, _l, _vp, _vp, _vp, _i, _i, _vp,
+                                     _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'pacoh_mlp_fused_split': (_i, [_i, _i, _i, _i]),
     'pacoh_mlp_fused_plan': (_i, [_i, _i, _i, _i, _i, _i, _ip, _ip, _ip]),
 }
@@ -724,6 +727,41 @@ def gp_lml_fwdbwd(z, z_div, mean, mean_mode, y, y_div, lengthscale, outputscale,
                                        _ptr(d_z), _ptr(d_mean), _ptr(d_ls), _ptr(d_os), _ptr(d_noise), _ptr(info),
                                        B, P, n, _kf(f, kernel), dtype_code(z), _stream()), 'pacoh_gp_lml_fwdbwd')
     return lml, d_z, d_mean, d_ls, d_os, d_noise, info
+
+
+def fwd_gp_applicable(B, P, n, x_div, d_in, hidden, f, has_outputscale, mean_mode, dtype, kernel=KERNEL_RBF):
+    """does fwd_gp_lml_fwdbwd cover this shape (host-side query)?"""
+    if FORCE_DENSE or dtype not in (torch.float32, torch.float64):
+        return False
+    code = F32 if dtype == torch.float32 else F64
+    return bool(load_library().pacoh_fwd_gp_applicable(B, P, n, x_div, d_in, _hidden_arr(hidden), len(hidden), _kf(f, kernel),
+                                                       int(bool(has_outputscale)), mean_mode, code))
+
+
+def fwd_gp_lml_fwdbwd(x, x_div, theta, P, d_in, hidden, off_mean, off_kernel, f, y, y_div, lengthscale, noise, B, n, n_valid=None,
+                      g_lml=None, stash=None, svgd_tail=None, active=None):
+    """mlp2_fwd (mean network at off_mean, kernel-feature network with f outputs at off_kernel) + gp_lml_fwdbwd on its outputs as ONE
+    launch (fwd_gp_applicable shapes only): the same results, bit for bit, without z / mean -> (lml, d_z, d_mean, d_ls, None, d_noise,
+    info).  stash / svgd_tail / active: as for mlp2_fwd"""
+    lib = load_library()
+    dev, dt = x.device, x.dtype
+    lml = torch.empty(B, dtype=dt, device=dev)
+    d_z = torch.empty(B, n, f, dtype=dt, device=dev)
+    d_mean = torch.empty(B, n, dtype=dt, device=dev)
+    d_ls = torch.empty(B, f, dtype=dt, device=dev)
+    d_noise = torch.empty(B, dtype=dt, device=dev)
+    info = torch.empty(B, dtype=torch.int32, device=dev)
+    act = _active_tasks(active)
+    sv_X, sv_ws, ctr = svgd_tail if svgd_tail is not None else (None, None, None)
+    with _Timed('gp_lml_fwdbwd'):
+        _check(lib.pacoh_fwd_gp_lml_fwdbwd(ctypes.byref(act) if act is not None else None, _ptr(x), x_div, _ptr(theta, x), theta.shape[1],
+                                           P, d_in, _hidden_arr(hidden), len(hidden), off_mean, off_kernel, _ptr(stash),
+                                           _ptr(sv_X, x), _ptr(sv_ws), sv_X.shape[0] if sv_X is not None else 0,
+                                           sv_X.shape[1] if sv_X is not None else 0, _ptr(ctr),
+                                           _ptr(y, x), y_div, _ptr(lengthscale, x), None, _ptr(noise, x), _ptr(n_valid), _ptr(g_lml, x),
+                                           _ptr(lml), _ptr(d_z), _ptr(d_mean), _ptr(d_ls), None, _ptr(d_noise), _ptr(info),
+                                           B, n, _kf(f, KERNEL_RBF), dtype_code(x), _stream()), 'pacoh_fwd_gp_lml_fwdbwd')
+    return lml, d_z, d_mean, d_ls, None, d_noise, info
 
 
 def gp_predict(z_ctx, z_div, mean_ctx, mean_mode, y, y_div, z_tst, zt_div, mean_tst, lengthscale, outputscale, noise,

@@ -223,6 +223,7 @@ __device__ __forceinline__ void factor16(f32x4 Cn, f32x4& Z, float& dprod, const
 // instead (a scalar-cache hit).
 struct KernelCtx {
     static constexpr bool TASK_WEIGHTS = true;     // (GpMfmaArgs::task_w is filled in by the caller: a host launch)
+    static constexpr bool LDS_INPUTS = false;      // (z and the mean vector are read from global memory: GpMfmaArgs::z / mean)
     __device__ __forceinline__ int lane() const { return threadIdx.x; }
     __device__ __forceinline__ unsigned block() const { return blockIdx.x; }
     template <typename T>
@@ -235,6 +236,7 @@ struct KernelCtx {
 // A wave of a larger workgroup working on problem `b` of an argument block held by the caller (map_persist.hip)
 struct WaveCtx {
     static constexpr bool TASK_WEIGHTS = false;    // (the argument block is built inside a kernel, field by field: no task weights there)
+    static constexpr bool LDS_INPUTS = false;
     unsigned b;
     __device__ __forceinline__ int lane() const { return threadIdx.x & 63; }
     __device__ __forceinline__ unsigned block() const { return b; }
@@ -347,7 +349,12 @@ __device__ __forceinline__ void gp_reg_body(const GpMfmaArgs& a, const Ctx& cx, 
     constexpr float SC = RegFam<FAM>::SC, DZ = RegFam<FAM>::DZ;
     float kls[FP];                                            // SC / lengthscale
 #pragma unroll
-    for (int c = 0; c < FP; ++c) kls[c] = (c < f) ? SC * rcp_(a.ls[(long)p * f + c]) : 1.0f;
+    for (int c = 0; c < FP; ++c) {
+        kls[c] = (c < f) ? SC * rcp_(a.ls[(long)p * f + c]) : 1.0f;
+        // (wave-uniform, and live to the last store: gp_fwd_reg.hip's kernel keeps them in scalar registers -- in vector registers it
+        //  spills them, as gp_reg_kernel<4, 2, true, false> does: profiles/fwd_gp_kernel_resources.txt)
+        if constexpr (Ctx::LDS_INPUTS) kls[c] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(kls[c])));
+    }
     const float os = HAS_OS ? (a.os ? a.os[p] : 1.0f) : 1.0f;
     const float noise = a.noise[p];
 
@@ -366,11 +373,13 @@ __device__ __forceinline__ void gp_reg_body(const GpMfmaArgs& a, const Ctx& cx, 
         zs[0] = 1e10f * (float)(i + 1);
         if (i < nv) {
             zs[0] = 0.0f;
-            const float* zp = a.z + ((long)(blk / (unsigned)a.z_div) * n + i) * (long)f;
+            // (Ctx::LDS_INPUTS -- gp_fwd_reg.hip: the caller's prologue has left row i's raw features in zf[i FP ..] and its prior mean
+            //  in rv[i], the slots this lane overwrites below; GpMfmaArgs::z / mean are not read)
+            const float* zp = Ctx::LDS_INPUTS ? zf + i * FP : a.z + ((long)(blk / (unsigned)a.z_div) * n + i) * (long)f;
 #pragma unroll
             for (int c = 0; c < FP; ++c) if (c < f) zs[c] = zp[c] * kls[c];
             float mi = 0.0f;
-            if (a.mean_mode == PACOH_MEAN_VECTOR) mi = a.mean[b * n + i];
+            if (a.mean_mode == PACOH_MEAN_VECTOR) mi = Ctx::LDS_INPUTS ? rv[i] : a.mean[b * n + i];
             else if (a.mean_mode == PACOH_MEAN_CONST) mi = a.mean[p];
             ri = a.y[ty * n + i] - mi;
         }

@@ -28,6 +28,7 @@
 #include "hyper_tail.h"
 #include "step_tail.h"
 #include "mlp_fused_split.h"
+#include "mlp_act.h"
 #include <stdlib.h>
 
 namespace pacoh {
@@ -98,15 +99,7 @@ __device__ __forceinline__ f32x4 fmfma(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-// tanh(y) = 1 - 2 / (1 + exp2(TSC y)), TSC = 2 log2(e).  The weights and biases of every tanh layer are multiplied by TSC when
-// they are copied to LDS, so the matrix cores deliver the exp2 argument itself and an activation costs v_exp + v_add + v_rcp +
-// v_fma (one instruction less, on each of the 64 activations per lane, tile and pass).  The backward pass multiplies by the
-// SCALED hidden weights in its delta recursion, so delta_l comes out as TSC^(NH - l) times the true one (l = 1..NH): the
-// accumulated weight gradients are scaled back once, where the slab is written.
-constexpr float TSC = 2.8853900817779268f, INV_TSC = 0.34657359027997264f;
-__device__ __forceinline__ float tanh_pre(float a) {
-    return fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(a)), 1.0f);
-}
+// (TSC, INV_TSC, tanh_pre: mlp_act.h -- tanh through exp2 on weights pre-multiplied by TSC)
 
 // zero-padded weights of one particle's network -> LDS (tanh layers pre-multiplied by TSC)
 template <int NH>

@@ -746,6 +746,20 @@ class GPEngine:
             return lay.block_range('mean_nn.')[0], lay.block_range('kernel_nn.')[0]
         return None
 
+    FWD_GP_MIN_PROBLEMS = 4096   # one resident round of the GP kernel: from there on the separate forward launch pays for a nearly
+                                 # empty last round of workgroups (profiles/fwd_gp_bench.txt)
+
+    def _use_fwd_gp(self, B, P, n, outputscale, dtype):
+        """lml_and_grad runs the two networks' forward inside the GP launch (L.fwd_gp_lml_fwdbwd): fp32, RBF without outputscale, paired
+        fused networks of 1-2 hidden layers, d_in <= 4, f <= 2, n == 64 -- from FWD_GP_MIN_PROBLEMS (task, parameter row) problems.
+        PACOH_FWD_GP=0 / 1: never / wherever eligible (tests, A/B)"""
+        force = os.environ.get('PACOH_FWD_GP')
+        lay = self.layout
+        if force == '0' or self._paired_nets() is None or (force != '1' and B < self.FWD_GP_MIN_PROBLEMS):
+            return False
+        return L.fwd_gp_applicable(B, P, n, P, lay.input_dim, list(lay.mean_nn_layers), lay.feature_dim, outputscale is not None,
+                                   L.MEAN_VECTOR, dtype, kernel=lay.kernel_code)
+
     def _features(self, theta, x, T, n, theta_per_task=False, keep=False, svgd_tail=None, active=None):
         """kernel inputs z (+ divisor) and mean (+ mode) for B = T*P problems (b = t*P + p: task t, parameter row p).
         theta_per_task: theta holds T*S rows, S of its own per task -- the same kernels with P = T*S parameter rows, ONE
@@ -827,7 +841,9 @@ class GPEngine:
         B = T * P
         dev, dt = theta.device, theta.dtype
         ls, os_, noise = hypers if hypers is not None else self._hypers(theta)      # (hypers: already transformed by pacoh_step_begin)
-        z, z_div, mean, mode = self._features(theta, batch.x, T, n, keep=True, svgd_tail=svgd_tail, active=active)
+        fwd_gp = self._use_fwd_gp(B, P, n, os_, dt)
+        if not fwd_gp:
+            z, z_div, mean, mode = self._features(theta, batch.x, T, n, keep=True, svgd_tail=svgd_tail, active=active)
         g = None                                        # weight 1: the kernels take g_lml = NULL
         if float(weight) != 1.0:
             gkey = ('g', B, dt, dev)                    # ONE upstream-gradient vector per batch shape, refilled when the weight changes
@@ -837,10 +853,21 @@ class GPEngine:
                 g.fill_(float(weight))
                 ent = self._ws[gkey] = (g, float(weight))
             g = ent[0]
-        lml, d_z, d_mean, d_ls, d_os, d_noise, info = L.gp_lml_fwdbwd(
-            z, z_div, mean, mode, batch.y, P, ls, os_, noise, B, P,
-            n_valid=batch.n_valid if batch.ragged else None, g_lml=g, want_dz=(lay.covar_module == 'NN'), kernel=lay.kernel_code,
-            active=active)
+        if fwd_gp:
+            # the two networks' forward runs inside the GP launch (csrc/gp_fwd_reg.hip): one launch less, z / mean stay on the chip
+            pair = self._paired_nets()
+            key = ('stash', B, n)                          # (as _features(keep=True): the backward below reads it)
+            stash = self._ws[key] = L.mlp2_stash(batch.x, P, lay.input_dim, list(lay.mean_nn_layers), 1, lay.feature_dim, B, n,
+                                                 self._ws.get(key))
+            lml, d_z, d_mean, d_ls, d_os, d_noise, info = L.fwd_gp_lml_fwdbwd(
+                batch.x, P, theta, P, lay.input_dim, list(lay.mean_nn_layers), pair[0], pair[1], lay.feature_dim, batch.y, P, ls, noise,
+                B, n, n_valid=batch.n_valid if batch.ragged else None, g_lml=g, stash=stash,
+                svgd_tail=svgd_tail[:3] if svgd_tail is not None else None, active=active)
+        else:
+            lml, d_z, d_mean, d_ls, d_os, d_noise, info = L.gp_lml_fwdbwd(
+                z, z_div, mean, mode, batch.y, P, ls, os_, noise, B, P,
+                n_valid=batch.n_valid if batch.ragged else None, g_lml=g, want_dz=(lay.covar_module == 'NN'), kernel=lay.kernel_code,
+                active=active)
         grad = grad_out if grad_out is not None else torch.empty(P, D, dtype=dt, device=dev)   # every block is written below
         pair = self._paired_nets()
         off_ls, f, off_os, off_noise, off_c = self._hyper_offsets()
