@@ -244,6 +244,38 @@ int pacoh_gp_path_eval(const void* zs, const void* v, const void* w, const int32
                        const void* lengthscale, const void* outputscale, void* out,
                        int B, int P, int n, int cap, int S, int D, int m, int f, int dtype, void* stream);
 
+/* ---- per-draw argmax / argmin of the posterior paths over a pool of candidates (csrc/gp_path.hip) -------------------------------
+ * What Thompson sampling asks of a function draw, without the [B,S,m] tensor of pacoh_gp_path_eval.  No reference lines stand
+ * behind these two either: the reference has no pathwise sampler (and no acquisition on one).
+ * For every problem b and draw s, over the ELIGIBLE test points t in [0, m) (mask NULL, or mask[t] != 0):
+ *   f(b,s,t) = exactly the value pacoh_gp_path_eval writes to out[b,s,t] for the same arguments (the same device code: bit for bit),
+ *   largest = 1: the t with the greatest f,  largest = 0: the t with the smallest f;
+ *   ties (==, so -0.0 ties with +0.0) go to the smaller global index idx_base + t; a NaN f never wins; a draw with no eligible,
+ *   non-NaN point gives best_idx = -1, best_val = NaN; a problem with info[b] < 0 always gives -1 / NaN.
+ * best_val[B*S] (the call's dtype) and best_idx[B*S] (int64, GLOBAL indices idx_base + t) are in/out: first = 1 ignores what they
+ * hold; first = 0 merges the pair they hold (idx < 0 or a NaN value: nothing) by the same rule, so a pool can be streamed in
+ * chunks of m candidates with idx_base = the chunk's offset, in any chunk order, in constant device memory.
+ * Two launches, no atomics, deterministic: (1) grid = problems x STRIPS of consecutive 64-point test tiles x groups of up to 64
+ * draws; a workgroup runs the K loop of pacoh_gp_path_eval tile by tile, reduces each draw's 64 values in LDS and keeps the
+ * running pair per draw, then writes ONE partial pair per (problem, draw, strip) into the workspace; (2) a wave per (problem,
+ * draw) merges the strips and, with first = 0, the pair already in best_*.
+ * strips = 0: ceil(32768 / B), at least 1, at most the number of tiles (one tile per strip is the fastest where it fits; the bound
+ * caps the partials of a very large call); strips > 0: that many,
+ * clamped to the number of tiles.  The result does not depend on strips.
+ * pacoh_gp_path_argmax_workspace_bytes: the bytes of partials of such a call (8 + sizeof(T) per pair); for strips = 0 an upper
+ *   bound that never shrinks as B or S grow.  0 for arguments the call itself refuses.
+ * Conventions, families and limits as pacoh_gp_path_eval (cosine family: PACOH_ELIMIT).  PACOH_EINVAL besides: strips < 0,
+ * idx_base < 0, largest / first not 0 or 1, best_val / best_idx / workspace NULL, workspace_bytes below the query.  Every check
+ * runs before anything is enqueued: a refused call launches nothing and leaves best_* as they were. */
+size_t pacoh_gp_path_argmax_workspace_bytes(int B, int S, int m, int strips, int dtype);
+int pacoh_gp_path_argmax(const void* zs, const void* v, const void* w, const int32_t* info,
+                         const void* omega, const void* phase,
+                         const void* z_tst, int zt_div, const void* mean_tst, int mean_mode,
+                         const void* lengthscale, const void* outputscale,
+                         const uint8_t* mask, void* best_val, int64_t* best_idx, void* workspace, size_t workspace_bytes,
+                         int B, int P, int n, int cap, int S, int D, int m, int f,
+                         int64_t idx_base, int largest, int first, int strips, int dtype, void* stream);
+
 /* ---- dense path (large n): Cholesky-based Gaussian log-density of materialised covariances -----
  * logp[b] = log N(resid[b]; 0, A[b]) * scale,  A[B,n,n] symmetric (lower triangle read), destroyed
  * (overwritten by its Cholesky factor).  With A from pacoh_gram_rbf_ard(..., add_noise_diag=1) and

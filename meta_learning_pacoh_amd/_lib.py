@@ -46,6 +46,9 @@ SIGNATURES = {
     'pacoh_gp_path_fit': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'pacoh_gp_path_eval': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp,
                                 _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'pacoh_gp_path_argmax_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
+    'pacoh_gp_path_argmax': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                  _i, _i, _i, _i, _i, _i, _i, _i, _c.c_int64, _i, _i, _i, _i, _vp]),
     'pacoh_gp_lml_fwdbwd': (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                  _i, _i, _i, _i, _i, _vp]),
     'pacoh_gp_predict_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
@@ -645,6 +648,59 @@ def gp_path_eval(zs, n, v, omega, phase, w, info, z_tst, zt_div, mean_tst, mean_
                                       zt_div, _ptr(mean_tst, zs), mean_mode, _ptr(lengthscale, zs), _ptr(outputscale, zs), _ptr(out),
                                       B, P, n, cap, S, D, m, _kf(f, kernel), dtype_code(zs), _stream()), 'pacoh_gp_path_eval')
     return out
+
+
+def gp_path_argmax(zs, n, v, omega, phase, w, info, z_tst, zt_div, mean_tst, mean_mode, lengthscale, outputscale, B, P,
+                   kernel=KERNEL_RBF, largest=True, mask=None, strips=0, idx_base=0, first=True, best=None):
+    """per draw, the eligible test point at which gp_path_eval's value (same arguments, bit for bit) is greatest (largest) or
+    smallest -> (best_val [B,S], best_idx int64 [B,S]); ties to the smaller global index idx_base + t, NaN never wins, nothing
+    eligible or info < 0: -1 / NaN.  mask: bool / uint8 [m], nonzero = eligible.  The [B,S,m] tensor is never formed: two launches
+    and a workspace of partial pairs.  first=False merges into best = (best_val, best_idx) of an earlier call (in place), so a pool
+    can be streamed in chunks; strips: the split of the test tiles over workgroups (0: chosen by the library; no effect on the
+    result)."""
+    lib = load_library()
+    _path_family(kernel)
+    if zs.dim() != 3 or zs.shape[0] != B or B <= 0 or P <= 0 or B % P:
+        raise ValueError('zs must be [B,cap,f] with B = %d a positive multiple of P = %d, got %s' % (B, P, tuple(zs.shape)))
+    cap, f = zs.shape[1], zs.shape[2]
+    dt, dev = zs.dtype, zs.device
+    S, D = _path_base(omega, phase, w, None, B, n, f, dt)
+    if tuple(v.shape) != (B, S, n) or v.dtype != dt:
+        raise ValueError('v must be %s [%d,%d,%d], got %s %s' % (dt, B, S, n, v.dtype, tuple(v.shape)))
+    if info.dtype != torch.int32 or info.numel() != B:
+        raise ValueError('info must be int32 [%d]' % B)
+    if z_tst.dim() != 3 or z_tst.shape[2] != f or z_tst.shape[0] * zt_div < B or z_tst.shape[1] < 1:
+        raise ValueError('z_tst must be [>= %d,m,%d] for zt_div %d, got %s' % (-(-B // max(1, zt_div)), f, zt_div, tuple(z_tst.shape)))
+    m = z_tst.shape[1]
+    if tuple(lengthscale.shape) != (P, f) or (outputscale is not None and outputscale.numel() != P):
+        raise ValueError('lengthscale must be [%d,%d], outputscale [%d]' % (P, f, P))
+    _cond_mean(mean_tst, mean_mode, B, P, m)
+    _cond_limits(n, cap, dt)
+    if mask is not None:
+        if mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (m,):
+            raise ValueError('mask must be bool or uint8 [%d], got %s %s' % (m, mask.dtype, tuple(mask.shape)))
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    strips, idx_base = int(strips), int(idx_base)
+    if strips < 0 or idx_base < 0:
+        raise ValueError('strips and idx_base must not be negative, got %d and %d' % (strips, idx_base))
+    if first:
+        best_val = torch.empty(B, S, dtype=dt, device=dev)
+        best_idx = torch.empty(B, S, dtype=torch.int64, device=dev)
+    else:
+        if best is None:
+            raise ValueError('first=False needs best=(best_val, best_idx) of an earlier call')
+        best_val, best_idx = best
+        if tuple(best_val.shape) != (B, S) or best_val.dtype != dt or tuple(best_idx.shape) != (B, S) or best_idx.dtype != torch.int64:
+            raise ValueError('best must be (%s [%d,%d], int64 [%d,%d])' % (dt, B, S, B, S))
+    nbytes = lib.pacoh_gp_path_argmax_workspace_bytes(B, S, m, strips, dtype_code(zs))
+    ws = torch.empty(max(1, (nbytes + 7) // 8), dtype=torch.int64, device=dev)
+    with _Timed('gp_path_argmax'):
+        _check(lib.pacoh_gp_path_argmax(_ptr(zs), _ptr(v, zs), _ptr(w, zs), _ptr(info), _ptr(omega, zs), _ptr(phase, zs), _ptr(z_tst, zs),
+                                        zt_div, _ptr(mean_tst, zs), mean_mode, _ptr(lengthscale, zs), _ptr(outputscale, zs),
+                                        _ptr(mask), _ptr(best_val, zs), _ptr(best_idx), _ptr(ws), nbytes,
+                                        B, P, n, cap, S, D, m, _kf(f, kernel), idx_base, int(bool(largest)), int(bool(first)), strips,
+                                        dtype_code(zs), _stream()), 'pacoh_gp_path_argmax')
+    return best_val, best_idx
 
 
 _DENSE_WS = {}

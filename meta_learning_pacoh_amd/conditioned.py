@@ -4,6 +4,8 @@
     mean, std = cond.predict(candidates)                   # no factorisation: a Gram tile and a triangular GEMM on the matrix cores
     cond.append(x_new, y_new)                              # bordered update of the stored factor
     paths = cond.sample_paths(16)                          # posterior function draws (paths.py): paths(candidates) -> [P * 16, m]
+    idx, value = paths.argmax(candidates)                  # each draw's best candidate, fused: no [P * 16, m] tensor, any pool size
+    idx, paths = cond.thompson(candidates, batch_size=4)   # a Thompson batch: 4 candidates, each the argmax of its own draw
 
 What predict() of the learners recomputes on every call (csrc/gp_cond.hip keeps it: the rows of L^-1 and alpha) is what gpytorch
 caches in its prediction strategy and updates in ExactGP.get_fantasy_model; the reference itself never reuses them.
@@ -12,6 +14,8 @@ Out of scope: the joint covariance (so no log_prob on this object: use predict(.
 DRAWS come from sample_paths(), which needs no covariance), the cosine kernel family in sample_paths(), several tasks in one object,
 ragged contexts (n_valid), the single-task learner GPRegressionLearned, contexts beyond _lib.gp_cond_max_n(dtype) points (there is
 no large-context path), and gradients."""
+import math
+
 import numpy as np
 import torch
 
@@ -110,3 +114,20 @@ class ConditionedGP:
                              like=None if like is None else like.base)
         snap = self._engine.cond_paths(st, base)
         return PosteriorPaths(self._engine, snap, self._norm_x, self._y_mean.reshape(-1)[0], self._y_std.reshape(-1)[0])
+
+    def thompson(self, candidates, batch_size=1, num_features=1024, mask=None, chunk=None, like=None):
+        """a batch of Thompson samples over a pool of candidates [m,d] -> (idx int64 [batch_size] on the device, paths).  With P
+        parameter rows, S = ceil(batch_size / P) function draws per row are taken (sample_paths) and each draw's argmax over the
+        eligible candidates found by the fused kernel (paths.argmax: any pool size); batch_size of the P S indices are returned,
+        chosen by a random permutation from torch's device generator -- the stratified sample of the equal-weight mixture that
+        paths.component documents.  idx is -1 where nothing was eligible; two draws may pick the same candidate.
+        mask / chunk as paths.argmax; like = the PosteriorPaths of the previous round (the same batch_size and num_features) to follow
+        the same prior functions after append().  The returned PosteriorPaths is what to pass as like= next round."""
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError('batch_size must be at least 1, got %d' % batch_size)
+        P = self._state.theta.shape[0]
+        paths = self.sample_paths(math.ceil(batch_size / P), num_features, like=like)
+        idx, _ = paths.argmax(candidates, mask=mask, chunk=chunk)
+        pick = torch.randperm(idx.shape[0], device=idx.device)[:batch_size]
+        return idx[pick], paths

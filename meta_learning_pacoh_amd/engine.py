@@ -1027,6 +1027,27 @@ class GPEngine:
         return L.gp_path_eval(snap.zs, snap.n, snap.v, snap.omega, snap.phase, snap.w, snap.info, zt, zt_div, mt, mode, ls, os_, P, P,
                               kernel=self.layout.kernel_code)
 
+    def cond_paths_argmax(self, snap, tst_x, largest=True, mask=None, chunk=None):
+        """per draw of a PathSnap, the eligible point of tst_x[m,d] at which cond_paths_eval's value is greatest (largest) or smallest
+        -> (val [P,S] in normalised space, idx int64 [P,S]; -1 / NaN where nothing is eligible), by the rule of L.gp_path_argmax.
+        mask: bool [m] on the device, True = eligible.  The pool is streamed in chunks of `chunk` candidates (None:
+        PATH_ARGMAX_CHUNK): per chunk the test features of that chunk only and one L.gp_path_argmax that merges into the running
+        pair, so neither [P,m,f] nor [P,S,m] exists for m > chunk"""
+        from .paths import chunk_ranges
+        P = snap.theta.shape[0]
+        m = tst_x.shape[0]
+        ls, os_, _ = snap.hypers
+        best = None
+        for lo, hi in chunk_ranges(m, PATH_ARGMAX_CHUNK if chunk is None else chunk):
+            zt, zt_div, mt, mode = self._features(snap.theta, tst_x[lo:hi].unsqueeze(0).contiguous(), 1, hi - lo)
+            best = L.gp_path_argmax(snap.zs, snap.n, snap.v, snap.omega, snap.phase, snap.w, snap.info, zt, zt_div, mt, mode, ls, os_,
+                                    P, P, kernel=self.layout.kernel_code, largest=largest,
+                                    mask=None if mask is None else mask[lo:hi], idx_base=lo, first=lo == 0, best=best)
+        return best
+
+
+PATH_ARGMAX_CHUNK = 131072        # candidates per launch of cond_paths_argmax: [P, chunk, f] features is all that is ever resident
+
 
 class PathSnap:
     """what GPEngine.cond_paths keeps of one set of draws: theta [P,D], hypers, zs [P,n,f], info [P], n, the base (omega, phase, w,
