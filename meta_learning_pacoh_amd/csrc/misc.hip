@@ -148,10 +148,10 @@ __global__ void __launch_bounds__(1024) svgd_median_large_kernel(const T* __rest
     if (threadIdx.x == 0) mids[blockIdx.x] = MedBits<T>::from(result);
 }
 
-// stage 2: bandwidth (median heuristic), kernel matrix and its row sums.  One workgroup; wave 0 finds the median.
+// stage 2: bandwidth (median heuristic) and kernel matrix.  One workgroup; wave 0 finds the median.
 template <typename T>
 __global__ void __launch_bounds__(256) svgd_kmat_kernel(const T* __restrict__ d2, T bandwidth, T* __restrict__ Kmat,
-                                                        T* __restrict__ rowsum, T* __restrict__ gamma_out,
+                                                        T* __restrict__ gamma_out,
                                                         T* __restrict__ bw_out, int P, const T* __restrict__ mids = nullptr) {
     __shared__ T gam_s;
     const int N = P * P;
@@ -181,18 +181,15 @@ __global__ void __launch_bounds__(256) svgd_kmat_kernel(const T* __restrict__ d2
     const T gam = gam_s;
     if (threadIdx.x == 0) *gamma_out = gam;
     for (int q = threadIdx.x; q < N; q += 256) Kmat[q] = t_exp<T>(-gam * d2[q]);
-    __syncthreads();
-    for (int i = threadIdx.x; i < P; i += 256) {
-        T s = 0;
-        for (int j = 0; j < P; ++j) s += t_exp<T>(-gam * d2[i * P + j]);
-        rowsum[i] = s;
-    }
 }
 
-// stage 3: phi[i,d] = (sum_j K_ij (s_jd - 2 gamma x_jd) + 2 gamma x_id rowsum_i) / P; one thread per (i, d)
+// stage 3: phi[i,d] = sum_j K_ij (s_jd + 2 gamma (x_id - x_jd)) / P; one thread per (i, d).  The repulsion is summed from the
+// differences x_i - x_j, as the reference's autograd forms it: x_id sum_j K_ij - sum_j K_ij x_jd is the same number, but its two
+// halves are 2 gamma |x| each, and with particles much closer to each other than to the origin (gamma |x|^2 >> 1; one particle or
+// identical particles: gamma = 1e8) their rounding is all that is left of the score
 template <typename T>
 __global__ void __launch_bounds__(256) svgd_phi_kernel(const T* __restrict__ X, const T* __restrict__ score,
-                                                       const T* __restrict__ Kmat, const T* __restrict__ rowsum,
+                                                       const T* __restrict__ Kmat,
                                                        const T* __restrict__ gamma_p, int neg, T* __restrict__ phi,
                                                        int P, int D) {
     const int i = blockIdx.y;
@@ -200,9 +197,10 @@ __global__ void __launch_bounds__(256) svgd_phi_kernel(const T* __restrict__ X, 
     if (d >= D) return;
     const T gam2 = T(2) * gamma_p[0];
     const T* Ki = Kmat + (long)i * P;                // wave-uniform -> scalar loads
+    const T xi = X[(long)i * D + d];
     T acc = 0;
-    for (int j = 0; j < P; ++j) acc = fma(Ki[j], score[(long)j * D + d] - gam2 * X[(long)j * D + d], acc);
-    const T r = (acc + gam2 * X[(long)i * D + d] * rowsum[i]) / T(P);
+    for (int j = 0; j < P; ++j) acc = fma(Ki[j], fma(gam2, xi - X[(long)j * D + d], score[(long)j * D + d]), acc);
+    const T r = acc / T(P);
     phi[(long)i * D + d] = neg ? -r : r;
 }
 
@@ -233,7 +231,7 @@ __global__ void __launch_bounds__(256) svgd_update_kernel(const T* __restrict__ 
     }
     if (step_counter && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *step_counter += 1;   // (as in adam_dev_kernel)
     __shared__ T Ki[PACOH_SVGD_MAX_PARTICLES];
-    __shared__ T gam_s, rowsum_s;
+    __shared__ T gam_s;
     __shared__ T sc_s[5];                                  // score scale, lr, Adam step size, sqrt of bias correction 2, eps
     const int i = blockIdx.y;
     // The kernel is a chain of L2 round trips, not arithmetic (P x 2 loads per thread behind the bandwidth / kernel-row phase of
@@ -262,10 +260,8 @@ __global__ void __launch_bounds__(256) svgd_update_kernel(const T* __restrict__ 
             else bw = svgd_median_bandwidth<T>(d2, P, lane);
         }
         const T gam = T(1) / (T(1e-8) + T(2) * bw * bw);
-        T ksum = 0;
-        for (int j = lane; j < P; j += 64) { const T kv = t_exp<T>(-gam * d2[i * P + j]); Ki[j] = kv; ksum += kv; }
-        const T rs = subwave_sum<T>(ksum, 64);
-        if (lane == 0) { gam_s = gam; rowsum_s = rs; if (bw_out && blockIdx.x == 0 && i == 0) *bw_out = bw; }
+        for (int j = lane; j < P; j += 64) Ki[j] = t_exp<T>(-gam * d2[i * P + j]);
+        if (lane == 0) { gam_s = gam; if (bw_out && blockIdx.x == 0 && i == 0) *bw_out = bw; }
     } else if (threadIdx.x == 64) {
         // the step scalars, fetched by a wave that only waits for the bandwidth phase anyway: in the pipelined step their address
         // hangs on the step counter (two dependent round trips, which would otherwise sit in front of the prefetch above)
@@ -284,7 +280,7 @@ __global__ void __launch_bounds__(256) svgd_update_kernel(const T* __restrict__ 
     for (int u = 0; u < PF; ++u) {
         if (u < npre) {
             const T sj = score_scale * spre[u] - pscale * (xpre[u] - md);
-            acc = fma(Ki[u], sj - gam2 * xpre[u], acc);
+            acc = fma(Ki[u], fma(gam2, xi - xpre[u], sj), acc);      // (the repulsion from differences: see svgd_phi_kernel)
         }
     }
     int j = npre;
@@ -295,7 +291,7 @@ __global__ void __launch_bounds__(256) svgd_update_kernel(const T* __restrict__ 
 #pragma unroll
         for (int u = 0; u < 10; ++u) {
             const T sj = score_scale * scv[u] - pscale * (xj[u] - md);
-            acc = fma(Ki[j + u], sj - gam2 * xj[u], acc);
+            acc = fma(Ki[j + u], fma(gam2, xi - xj[u], sj), acc);
         }
     }
     for (; j + 4 <= P; j += 4) {
@@ -305,15 +301,15 @@ __global__ void __launch_bounds__(256) svgd_update_kernel(const T* __restrict__ 
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const T sj = score_scale * sc4[u] - pscale * (xj[u] - md);
-            acc = fma(Ki[j + u], sj - gam2 * xj[u], acc);
+            acc = fma(Ki[j + u], fma(gam2, xi - xj[u], sj), acc);
         }
     }
     for (; j < P; ++j) {
         const T xj = X[(long)j * D + d];
         const T sj = score_scale * score[(long)j * D + d] - pscale * (xj - md);
-        acc = fma(Ki[j], sj - gam2 * xj, acc);
+        acc = fma(Ki[j], fma(gam2, xi - xj, sj), acc);
     }
-    const T r = (acc + gam2 * xi * rowsum_s) / T(P);          // phi[i,d]
+    const T r = acc / T(P);                                   // phi[i,d]
     T xn;
     if (use_adam) {
         const T g = -r;                                       // particles.grad = -phi (svgd.py:27)
@@ -1093,18 +1089,17 @@ static int svgd_launch(const void* X, const void* score, double bandwidth, int n
                        void* workspace, int P, int D, hipStream_t s) {
     T* d2 = (T*)workspace;
     T* Kmat = d2 + P * P;
-    T* rowsum = Kmat + P * P;
-    T* gamma = rowsum + P;
-    T* mids = nullptr;                                // (the workspace has 8 spare elements behind rowsum: [0] gamma, [2..3] median pair)
+    T* gamma = Kmat + P * P + P;                      // (P elements behind the kernel matrix are unused)
+    T* mids = nullptr;                                // (the workspace has 8 spare elements there: [0] gamma, [2..3] median pair)
     hipLaunchKernelGGL(svgd_dist_kernel<T>, dim3(P * P), dim3(256), 0, s, (const T*)X, d2, P, D);
     if (P > 64 && !(bandwidth > 0.0)) {
         mids = gamma + 2;
         hipLaunchKernelGGL(svgd_median_large_kernel<T>, dim3(2), dim3(1024), 0, s, (const T*)d2, P, mids);
     }
     hipLaunchKernelGGL(svgd_kmat_kernel<T>, dim3(1), dim3(256), 0, s, (const T*)d2, (T)bandwidth, Kmat,
-                       rowsum, gamma, (T*)bw_out, P, (const T*)mids);
+                       gamma, (T*)bw_out, P, (const T*)mids);
     hipLaunchKernelGGL(svgd_phi_kernel<T>, dim3((D + 255) / 256, P), dim3(256), 0, s,
-                       (const T*)X, (const T*)score, (const T*)Kmat, (const T*)rowsum, (const T*)gamma, neg, (T*)phi, P, D);
+                       (const T*)X, (const T*)score, (const T*)Kmat, (const T*)gamma, neg, (T*)phi, P, D);
     return launch_status();
 }
 

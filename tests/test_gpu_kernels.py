@@ -847,7 +847,9 @@ def test_svgd_many_particles(L, P):
 
 
 @pytest.mark.parametrize('dtype', [torch.float32, torch.float64])
-@pytest.mark.parametrize('P,optimizer,kernel', [(7, 'Adam', 'RBF'), (70, 'SGD', 'RBF'), (5, 'Adam', 'COS')])
+@pytest.mark.parametrize('P,optimizer,kernel', [(7, 'Adam', 'RBF'), (70, 'SGD', 'RBF'), (5, 'Adam', 'COS'),
+                                                # the riding bandwidth block at the register sort's 8, 16 and 32 values per lane
+                                                (24, 'Adam', 'RBF'), (33, 'SGD', 'RBF'), (46, 'Adam', 'RBF'), (64, 'SGD', 'RBF')])
 def test_pipelined_step_entry_points(L, dtype, P, optimizer, kernel):
     """pacoh_svgd_dist_advance + pacoh_svgd_update_next (csrc/step_tail.h) through the ABI: counter protocol, the update against the
     oracle's phi + torch optimizer with the scalars of the row the counter selects, softplus of the updated hyper-parameter entries,

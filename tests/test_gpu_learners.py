@@ -751,6 +751,9 @@ def test_graph_replay_is_bit_identical_to_eager_launches(M, kind, layers, monkey
     dict(mean_module='constant', covar_module='NN', feature_dim=3),                  # one network
     dict(optimizer='SGD', bandwidth=0.7),
     dict(num_particles=70),                                                         # median of > 64 particles: its own launch stays
+    # the bandwidth block riding in the fused MLP backward at the register sort's 8, 16 and 32 values per lane (24 .. 32, 33 .. 45,
+    # 46 .. 64 particles; 50 is the reference sweeps' larger count)
+    dict(num_particles=24), dict(num_particles=40), dict(num_particles=50), dict(num_particles=64),
 ])
 @pytest.mark.parametrize('graph', ['0', '1'])
 def test_pipelined_svgd_step_equals_the_step_begin_sequence(M, cfg, graph, monkeypatch):
