@@ -774,6 +774,49 @@ int pacoh_mixture_icdf(const void* mu, const void* var, const void* quantile, vo
                        double hi, double eps, int max_iter, int closed_form, int P, int m, int dtype, void* stream);
 int pacoh_calib_error(const void* cdf, void* out, int T, int m, int dtype, void* stream);
 
+/* ---- analytic acquisition on the posterior predictive, with a fused argmax (csrc/acq.hip) ---------------------------------------
+ * What a BO / active-learning loop asks first of a candidate pool: score it and return the best candidate.  No reference lines stand
+ * behind these two: the reference has no acquisition function.  The specification is meta_learning_pacoh_amd/acquisition.py
+ * (mixture_acquisition, pure torch), which the kernel follows operation by operation in the working precision (erfc / exp of the
+ * device library, nothing contracted to an fma).
+ * mu, var [T*P, m] are the predictive moments of T tasks x P parameter rows in normalised space, problem b = t P + p: exactly what
+ * pacoh_gp_cond_predict and pacoh_gp_predict write.  noise [P] | NULL: subtracted from every row's variance (the latent function);
+ * a variance below 0 counts as 0.  Per task t and candidate j the value of the equal-weight mixture over the P rows is
+ *   kind = PACOH_ACQ_MEAN / _STD / _UCB: M, sd, M + sign beta sd, with M and sd the mixture's mean and standard deviation (Welford's
+ *          update over the rows: sd^2 = mean_p v_p + mean_p (mu_p - M)^2);
+ *   kind = PACOH_ACQ_EI / _PI: mean_p of the row's expected improvement s (z Phi(z) + phi(z)), clamped at 0, / probability of
+ *          improvement Phi(z), z = (sign (mu_p - best) - xi) / s, s = sqrt(v_p); s == 0: max(d, 0) / (d > 0), d = z s.
+ * sign = +1: a larger target is better; -1: a smaller one (improvement is best - mu; _UCB is the lower confidence bound).
+ * One scalar best / xi / beta serves all T tasks.  A NaN moment that the kind reads makes the value NaN.
+ * values [T,m] | NULL receives the values.  best_val [T] (the call's dtype) and best_idx [T] (int64, GLOBAL indices idx_base + j)
+ * receive, per task, the eligible candidate (mask NULL, or mask[j] != 0) with the greatest (largest = 1) or smallest value by the
+ * selection rule of pacoh_gp_path_argmax, in its words: ties (==) go to the smaller global index, a NaN value never wins, nothing
+ * eligible gives -1 / NaN; first = 1 ignores what best_* hold, first = 0 merges the pair they hold (idx < 0 or a NaN value:
+ * nothing) by the same rule, so a pool can be streamed in chunks with idx_base = the chunk's offset, in any chunk order.  The entry
+ * keeps `largest` free; a caller wants 1 except for _MEAN / _UCB with sign = -1.
+ * Two launches, no atomics, deterministic: (1) grid = tasks x STRIPS of consecutive 256-point blocks, 256 threads; a thread walks the
+ * P rows of its points, keeps its running pair, the block reduces the 256 pairs (shuffles, then four pairs through LDS) and writes
+ * ONE partial pair per (task, strip) into the workspace; (2) a wave per task merges the strips and, with first = 0, best_*.
+ * strips = 0: ceil(32768 / T), at least 1, at most the number of blocks (one block per strip where that fits; the bound caps the
+ * partials); strips > 0: that many, clamped to the number of blocks.  The result does not depend on strips.
+ * pacoh_mixture_acq_workspace_bytes: the bytes of partials of such a call (8 + sizeof(T) per pair); for strips = 0 an upper bound
+ *   that never shrinks as T or m grow.  0 for arguments the call itself refuses.
+ * Limits as pacoh_mixture_cdf: 1 <= T <= 65535 (beyond: PACOH_ELIMIT), P >= 1, m >= 1.  PACOH_EINVAL: T, P or m < 1, kind not one of
+ * the five, sign not +1 / -1, strips < 0, idx_base < 0, largest / first not 0 or 1, mu / var / best_val / best_idx / workspace NULL,
+ * workspace_bytes below the query.  Every check runs before anything is enqueued: a refused call launches nothing and leaves
+ * best_* and values as they were. */
+#define PACOH_ACQ_EI 0
+#define PACOH_ACQ_PI 1
+#define PACOH_ACQ_UCB 2
+#define PACOH_ACQ_MEAN 3
+#define PACOH_ACQ_STD 4
+
+size_t pacoh_mixture_acq_workspace_bytes(int T, int m, int strips, int dtype);
+int pacoh_mixture_acq(const void* mu, const void* var, const void* noise, const uint8_t* mask,
+                      void* values, void* best_val, int64_t* best_idx, void* workspace, size_t workspace_bytes,
+                      int kind, double best, double xi, double beta, int sign,
+                      int T, int P, int m, int64_t idx_base, int largest, int first, int strips, int dtype, void* stream);
+
 /* ---- 8g: joint draws from the posterior predictive ----------------------------------------------------------------------------
  * The reference's predictive AffineTransformedDistribution(likelihood(gp(x))) (meta_learn/models.py:15-43, returned by
  * GPR_meta_mll.py:181-186 and GPR_mll.py:194-198) draws with MultivariateNormal.rsample: gpytorch's psd_safe_cholesky of the

@@ -117,6 +117,9 @@ SIGNATURES = {
     'pacoh_mixture_cdf': (_i, [_vp, _vp, _vp, _vp, _d, _d, _i, _i, _i, _i, _vp]),
     'pacoh_mixture_icdf': (_i, [_vp, _vp, _vp, _vp, _d, _d, _d, _d, _d, _i, _i, _i, _i, _i, _vp]),
     'pacoh_calib_error': (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    'pacoh_mixture_acq_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'pacoh_mixture_acq': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _d, _d, _d, _i, _i, _i, _i, _c.c_int64,
+                               _i, _i, _i, _i, _vp]),
     'pacoh_mvn_factor_workspace_bytes': (_sz, [_i, _i, _i]),
     'pacoh_mvn_factor': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     'pacoh_mvn_sample': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _i, _i, _i, _i, _vp]),
@@ -1679,6 +1682,56 @@ def mixture_icdf(mu_n, var_n, quantile, y_mean, y_std, closed_form=False, lo=-1e
                                       float(lo), float(hi), float(eps), int(max_iter), int(bool(closed_form)), P, m,
                                       dtype_code(mu_n), _stream()), 'pacoh_mixture_icdf')
     return out
+
+
+def mixture_acq(mu, var, T, P, kind, best, xi, beta, sign, noise=None, mask=None, want_values=False, largest=True, strips=0,
+                idx_base=0, first=True, best_pair=None):
+    """analytic acquisition of the equal-weight mixture of the P rows of each of T tasks at m candidates, with the argmax fused:
+    mu, var [T*P,m] or [T,P,m] (normalised space; what gp_cond_predict / gp_predict return) -> (best_val [T], best_idx int64 [T],
+    values [T,m] | None).  kind: 'ei' / 'pi' / 'ucb' / 'mean' / 'std' by the rule of acquisition.mixture_acquisition, with the
+    scalars best, xi, beta and sign = +1 / -1 of that function; noise [P] | None is subtracted from the rows' variances.
+    The pair is the eligible candidate (mask: bool / uint8 [m], nonzero = eligible) with the greatest (largest) or smallest value by
+    the rule of gp_path_argmax: ties to the smaller global index idx_base + j, NaN never wins, nothing eligible: -1 / NaN.
+    first=False merges into best_pair = (best_val, best_idx) of an earlier call (in place), so a pool can be streamed in chunks;
+    strips: the split of the 256-point blocks over workgroups (0: chosen by the library; no effect on the result)."""
+    from .acquisition import kind_code
+    lib = load_library()
+    code = kind_code(kind)
+    T, P = int(T), int(P)
+    if mu.dim() not in (2, 3) or mu.shape != var.shape or T < 1 or P < 1 or mu.shape[-1] < 1 or mu.numel() != T * P * mu.shape[-1]:
+        raise ValueError('mu and var must both be [%d,m] or [%d,%d,m], got %s and %s' % (T * P, T, P, tuple(mu.shape), tuple(var.shape)))
+    if var.dtype != mu.dtype:
+        raise ValueError('mu and var must have one dtype, got %s and %s' % (mu.dtype, var.dtype))
+    dt, dev, m = mu.dtype, mu.device, mu.shape[-1]
+    if sign not in (1, -1):
+        raise ValueError('sign must be +1 or -1, got %r' % (sign,))
+    if noise is not None and (noise.numel() != P or noise.dtype != dt):
+        raise ValueError('noise must be %s [%d], got %s %s' % (dt, P, noise.dtype, tuple(noise.shape)))
+    if mask is not None:
+        if mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (m,):
+            raise ValueError('mask must be bool or uint8 [%d], got %s %s' % (m, mask.dtype, tuple(mask.shape)))
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    strips, idx_base = int(strips), int(idx_base)
+    if strips < 0 or idx_base < 0:
+        raise ValueError('strips and idx_base must not be negative, got %d and %d' % (strips, idx_base))
+    if first:
+        best_val = torch.empty(T, dtype=dt, device=dev)
+        best_idx = torch.empty(T, dtype=torch.int64, device=dev)
+    else:
+        if best_pair is None:
+            raise ValueError('first=False needs best_pair=(best_val, best_idx) of an earlier call')
+        best_val, best_idx = best_pair
+        if tuple(best_val.shape) != (T,) or best_val.dtype != dt or tuple(best_idx.shape) != (T,) or best_idx.dtype != torch.int64:
+            raise ValueError('best_pair must be (%s [%d], int64 [%d])' % (dt, T, T))
+    code_dt = dtype_code(mu)
+    values = torch.empty(T, m, dtype=dt, device=dev) if want_values else None
+    nbytes = lib.pacoh_mixture_acq_workspace_bytes(T, m, strips, code_dt)
+    ws = torch.empty(max(1, (nbytes + 7) // 8), dtype=torch.int64, device=dev)
+    with _Timed('mixture_acq'):
+        _check(lib.pacoh_mixture_acq(_ptr(mu), _ptr(var, mu), _ptr(noise, mu), _ptr(mask), _ptr(values, mu), _ptr(best_val, mu),
+                                     _ptr(best_idx), _ptr(ws), nbytes, code, float(best), float(xi), float(beta), int(sign), T, P, m,
+                                     idx_base, int(bool(largest)), int(bool(first)), strips, code_dt, _stream()), 'pacoh_mixture_acq')
+    return best_val, best_idx, values
 
 
 def mvn_factor(cov):

@@ -6,6 +6,8 @@
     paths = cond.sample_paths(16)                          # posterior function draws (paths.py): paths(candidates) -> [P * 16, m]
     idx, value = paths.argmax(candidates)                  # each draw's best candidate, fused: no [P * 16, m] tensor, any pool size
     idx, paths = cond.thompson(candidates, batch_size=4)   # a Thompson batch: 4 candidates, each the argmax of its own draw
+    ei = cond.acquisition('ei', candidates)                # analytic acquisition ('ei', 'pi', 'ucb', 'mean', 'std') -> [m], original units
+    idx, value = cond.acquire('ei', candidates, mask=free) # its best candidate, fused behind predict: no [P, m] values kept, any pool size
 
 What predict() of the learners recomputes on every call (csrc/gp_cond.hip keeps it: the rows of L^-1 and alpha) is what gpytorch
 caches in its prediction strategy and updates in ExactGP.get_fantasy_model; the reference itself never reuses them.
@@ -13,13 +15,15 @@ caches in its prediction strategy and updates in ExactGP.get_fantasy_model; the 
 Out of scope: the joint covariance (so no log_prob on this object: use predict(..., return_density=True) of the learner; joint
 DRAWS come from sample_paths(), which needs no covariance), the cosine kernel family in sample_paths(), several tasks in one object,
 ragged contexts (n_valid), the single-task learner GPRegressionLearned, contexts beyond _lib.gp_cond_max_n(dtype) points (there is
-no large-context path), and gradients."""
+no large-context path), gradients, and of the acquisition functions (acquisition.py): batch / q-acquisition and top-k, look-ahead
+acquisition (knowledge gradient), a log-EI, and a per-task incumbent."""
 import math
 
 import numpy as np
 import torch
 
 from . import _lib as L
+from . import acquisition as A
 from .distributions import GaussianPredictive
 from .paths import PosteriorPaths, check_base, draw_base
 from .util import _handle_input_dimensionality
@@ -114,6 +118,46 @@ class ConditionedGP:
                              like=None if like is None else like.base)
         snap = self._engine.cond_paths(st, base)
         return PosteriorPaths(self._engine, snap, self._norm_x, self._y_mean.reshape(-1)[0], self._y_std.reshape(-1)[0])
+
+    def _acq(self, kind, candidates, best_f, xi, beta, maximize, observation_noise, mask, chunk, want_values):
+        A.kind_code(kind)
+        st = self._state
+        xn = self._norm_x(candidates)
+        if mask is not None:
+            mask = torch.as_tensor(mask, dtype=torch.bool).reshape(-1).to(xn.device).contiguous()
+            if mask.shape[0] != xn.shape[0]:
+                raise ValueError('mask must be [%d], got %s' % (xn.shape[0], tuple(mask.shape)))
+        y_mean, y_std = self._y_mean.reshape(-1)[0], self._y_std.reshape(-1)[0]
+        best_n, xi_n = 0.0, 0.0
+        if kind in ('ei', 'pi'):
+            if best_f is None:                   # the best observed target of the context, already normalised (one host sync)
+                seen = st.ctx_y[:st.n]
+                best_n, xi_n = float(seen.max() if maximize else seen.min()), float(xi) / float(y_std)
+            else:
+                best_n, xi_n = A.to_normalised(best_f, xi, y_mean, y_std)
+        val, idx, values = self._engine.cond_acq(st, xn, kind, best_n, xi_n, float(beta), 1 if maximize else -1,
+                                                 not observation_noise, mask, chunk, want_values)
+        return (idx[0], A.to_original(val[0], kind, y_mean, y_std),
+                None if values is None else A.to_original(values, kind, y_mean, y_std))
+
+    def acquisition(self, kind, candidates, best_f=None, xi=0.0, beta=2.0, maximize=True, observation_noise=False):
+        """the analytic acquisition function `kind` at candidates [m,d] -> tensor [m] on the device, in original units: 'ei' expected
+        improvement over best_f by more than xi, 'pi' its probability, 'ucb' mean + beta std (maximize=False: the lower confidence
+        bound mean - beta std), 'mean', 'std'.  SVGD / VI-Bayes: of the equal-weight mixture over the rows ('ei' / 'pi': the mean of
+        the rows' values; 'ucb' / 'mean' / 'std': the mixture's moments) -- acquisition.mixture_acquisition is the rule, one fused
+        launch behind the predict launch computes it (csrc/acq.hip).
+        best_f: the incumbent in original units (None: the best observed target of the conditioned context; only 'ei' / 'pi' read
+        it).  maximize=False: a smaller target is better.  observation_noise=False (the default) scores the latent function, as BO
+        libraries do; True scores the noisy target that predict() describes."""
+        return self._acq(kind, candidates, best_f, xi, beta, maximize, observation_noise, None, None, True)[2]
+
+    def acquire(self, kind, candidates, best_f=None, xi=0.0, beta=2.0, maximize=True, observation_noise=False, mask=None, chunk=None):
+        """the best candidate by acquisition(...) -> (idx int64 scalar tensor on the device, value scalar tensor in original units):
+        the greatest value ('mean' / 'ucb' with maximize=False: the smallest), ties to the smaller index, NaN never wins, idx -1 and
+        value NaN when nothing is eligible.  The values are not kept: the pool is streamed in chunks of `chunk` candidates (None:
+        131 072) through predict + the fused kernel, so it can be of any size.  mask: bool tensor or array [m], True = eligible."""
+        idx, val, _ = self._acq(kind, candidates, best_f, xi, beta, maximize, observation_noise, mask, chunk, False)
+        return idx, val
 
     def thompson(self, candidates, batch_size=1, num_features=1024, mask=None, chunk=None, like=None):
         """a batch of Thompson samples over a pool of candidates [m,d] -> (idx int64 [batch_size] on the device, paths).  With P

@@ -90,6 +90,24 @@ class GaussianPredictive:
         return L.mixture_icdf(self._mu_n.contiguous(), self._var_n.contiguous(), quantile, self.y_mean, self.y_std,
                               closed_form=not self.mixture)
 
+    def acquisition(self, kind, best_f=None, xi=0.0, beta=2.0, maximize=True):
+        """the analytic acquisition function `kind` ('ei', 'pi', 'ucb', 'mean', 'std'; acquisition.py) at the m test points this
+        object holds -> tensor [m] in original units, one fused launch.  Mixture: of the equal-weight mixture over the num_dists
+        components; else of the single component.  The variance is the one held here, observation noise included.  best_f (original
+        units) is the incumbent 'ei' / 'pi' improve on: required for them.  maximize=False: a smaller target is better."""
+        from . import acquisition as A
+        A.kind_code(kind)
+        best_n, xi_n = 0.0, 0.0
+        if kind in ('ei', 'pi'):
+            if best_f is None:
+                raise ValueError("best_f (the incumbent, in original units) is required for %r" % kind)
+            best_n, xi_n = A.to_normalised(best_f, xi, self.y_mean, self.y_std)
+        P = self.num_dists if self.mixture else 1
+        sign = 1 if maximize else -1
+        _, _, values = L.mixture_acq(self._mu_n[:P].contiguous(), self._var_n[:P].contiguous(), 1, P, kind, best_n, xi_n, float(beta),
+                                     sign, want_values=True, largest=not (kind in ('mean', 'ucb') and sign == -1))
+        return A.to_original(values[0], kind, self.y_mean, self.y_std)
+
     # -- joint draws ------------------------------------------------------------------------------
     def _factor(self):
         """the Cholesky factors of the P component covariances with gpytorch's jitter ladder, computed on the first draw (one host

@@ -1045,8 +1045,33 @@ class GPEngine:
                                     mask=None if mask is None else mask[lo:hi], idx_base=lo, first=lo == 0, best=best)
         return best
 
+    # -- analytic acquisition on the conditioned predictive (csrc/acq.hip) -----------------------------------------------------------
+    def cond_acq(self, st, tst_x, kind, best_n=0.0, xi_n=0.0, beta=2.0, sign=1, latent=True, mask=None, chunk=None, want_values=False):
+        """score tst_x[m,d] with the acquisition `kind` of the equal-weight mixture of the conditioned task's parameter rows and find
+        its best eligible point -> (val [1] in normalised space, idx int64 [1]; -1 / NaN where nothing is eligible, values [m] | None),
+        by the rule of L.mixture_acq.  latent: the rows' noise is taken off their predictive variance (the latent function).
+        mask: bool [m] on the device, True = eligible.  The pool is streamed in chunks of `chunk` candidates (None: PATH_ARGMAX_CHUNK):
+        per chunk one cond_predict of that chunk and one L.mixture_acq that merges into the running pair, so at most [P, chunk]
+        moments are ever resident.  'mean' / 'ucb' with sign = -1 look for the smallest value, everything else for the greatest."""
+        from .paths import chunk_ranges
+        P = st.theta.shape[0]
+        m = tst_x.shape[0]
+        noise = st.hypers[2].reshape(-1).contiguous() if latent else None
+        largest = not (kind in ('mean', 'ucb') and sign == -1)
+        best, vals = None, []
+        for lo, hi in chunk_ranges(m, PATH_ARGMAX_CHUNK if chunk is None else chunk):
+            mu, var = self.cond_predict(st, tst_x[lo:hi])
+            bv, bi, v = L.mixture_acq(mu, var, 1, P, kind, best_n, xi_n, beta, sign, noise=noise,
+                                      mask=None if mask is None else mask[lo:hi], want_values=want_values, largest=largest,
+                                      idx_base=lo, first=lo == 0, best_pair=best)
+            best = (bv, bi)
+            if want_values:
+                vals.append(v[0])
+        values = None if not want_values else (vals[0] if len(vals) == 1 else torch.cat(vals))
+        return best[0], best[1], values
 
-PATH_ARGMAX_CHUNK = 131072        # candidates per launch of cond_paths_argmax: [P, chunk, f] features is all that is ever resident
+
+PATH_ARGMAX_CHUNK = 131072       # candidates per launch of cond_paths_argmax: [P, chunk, f] features is all that is ever resident
 
 
 class PathSnap:
